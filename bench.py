@@ -1,6 +1,14 @@
 """Benchmark: partitioned 2-state pattern (config P3) on MI355X via libsiddhi_hip.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config P3|P3-dense|P1|W2-length|W2-time]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints the result line.
+--full adds what takes runs of its own: the calibration step behind `derived`
+and `roofline`, the CPU baselines, the parity_prefix / derived_check
+comparison with the CPU oracle, and at N > 1 the prepartitioned measurement
+alongside; without it those fields of the line are null.
+--dump-outputs DIR writes the rows of one step as DIR/<name>.npy (dump_rows).
 
 Workload (BASELINE.json configs[2]): P1's query
 `every e1=StockStream[price>70] -> e2=StockStream[symbol==e1.symbol and
@@ -41,7 +49,13 @@ def parse():
     ap.add_argument("--no-share", action="store_true", help="M5: every query scans alone (no shd_group)")
     ap.add_argument("--m5-direct", action="store_true",
                     help="M5 parity: every query against its own oracle run over the prefix (no leader lemma)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="oracle sample size for cpu_baseline (0=skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the calibration step (derived, roofline), the CPU baselines, the oracle comparison "
+                         "(parity_prefix, derived_check) and at N > 1 the prepartitioned measurement alongside")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the output rows of one step as DIR/<name>.npy")
+    ap.add_argument("--cpu-sample", type=int, default=-1,
+                    help="with --full: oracle sample size for cpu_baseline (0=skip)")
     ap.add_argument("--cpu-threads", type=int, default=16,
                     help="host threads of the per-key parallel CPU baseline (partitioned configs; 0=skip)")
     ap.add_argument("--key-base", type=int, default=-1,
@@ -132,6 +146,47 @@ def alg_bytes_window(c, n, n_out):
     """B_ev = 20 (in) + 12 (re-read at expiry) + 36*o per event."""
     o = c["matches"] / max(n, 1)
     return (20 + 12 + 36 * o) * n, dict(o=o)
+
+
+DUMP_LIMIT = 64 << 20   # bytes of .npy payload per --dump-outputs directory
+
+
+def dump_rows(out_dir, parts, output_types, suffix=""):
+    """--dump-outputs: the rows a caller polling after every push receives over
+    one step (`parts`: DeviceQuery.poll() results in push order), as float64
+    arrays: chunk (callback chunk id of the k-th poll that had rows, as k * 2^32 + id),
+    type, ts, nulls (rows x columns) and values (rows x columns; double and
+    float columns decoded, every other type as its integer value).  Beyond
+    DUMP_LIMIT bytes in all, a fixed seeded sample of the rows (rows.npy holds
+    their indices; all rows otherwise)."""
+    nc = len(output_types)
+    if parts:
+        chunk = np.concatenate([p[0] + (k << 32) for k, p in enumerate(parts)])
+        typ, ts, raw, nul = (np.concatenate([p[j] for p in parts]) for j in (1, 2, 3, 4))
+    else:
+        chunk, typ, ts = np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int64)
+        raw, nul = np.zeros((0, nc), np.uint64), np.zeros((0, nc), np.uint8)
+    n = len(ts)
+    rows = np.arange(n, dtype=np.int64)
+    per_row = 8 * (4 + 2 * raw.shape[1])
+    if n * per_row > DUMP_LIMIT:
+        keep = DUMP_LIMIT // per_row
+        rows = np.sort(np.random.default_rng(20261015).choice(n, size=keep, replace=False)).astype(np.int64)
+    raw = np.ascontiguousarray(raw[rows])
+    values = np.empty(raw.shape, np.float64)
+    for c in range(raw.shape[1]):
+        t = output_types[c] if c < nc else -1
+        if t == 4:
+            values[:, c] = raw[:, c].view(np.float64)
+        elif t == 3:
+            values[:, c] = raw[:, c].astype(np.uint32).view(np.float32)
+        else:
+            values[:, c] = raw[:, c].view(np.int64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("rows", rows), ("chunk", chunk[rows]), ("type", typ[rows]), ("ts", ts[rows]),
+                    ("nulls", nul[rows]), ("values", values)):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.asarray(a, dtype=np.float64))
+    return n, len(rows)
 
 
 def pmc_summary(cfg_name):
@@ -460,7 +515,7 @@ def run_multi(args, torch, dist, rank, world, local, dev):
             grp.close()
     for dq in dqs.values():
         dq.close()
-    if rank == 0 and args.cpu_sample != 0:
+    if rank == 0 and args.full and args.cpu_sample != 0:
         sample = min(n, args.cpu_sample if args.cpu_sample > 0 else 200_000)
         line["parity_prefix"], line["cpu_baseline"] = m5_parity_prefix(
             he, qa, queries, plans, d, sym, price, vol, ts, sample, keys, delta, not args.no_share, args.m5_direct)
@@ -735,6 +790,10 @@ def _first_query(app):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.e2e or args.config == "M5"):
+        raise SystemExit("--dump-outputs writes the rows of a single-query config (not --e2e, not M5)")
     if args.e2e:
         run_e2e(args)
         return
@@ -786,7 +845,7 @@ def main():
     if mode == "slices" and pattern:
         raise SystemExit("--input slices is for the (unpartitioned) window configs")
 
-    def measure(mode):
+    def measure(mode, dump=True):
         kb = None
         # inputs resident in HBM before the timed region
         if mode == "prepartitioned":
@@ -844,7 +903,8 @@ def main():
             for a, b in zip(cuts[:-1], cuts[1:]):
                 call_offsets_of(offs_all, a, b, co_cache)
 
-        def run_step(collect=None, cuts=cuts):
+        def run_step(collect=None, cuts=cuts, rows=None):
+            """rows: a list to poll every push's rows into (--dump-outputs) instead of dropping them."""
             dq.reset()
             tot = {}
             if take[0]:
@@ -905,7 +965,12 @@ def main():
                     torch.cuda.current_stream().synchronize()   # routed columns complete before the engine's stream reads them
                     dq.push_raw(0, m, rt.data_ptr(), [rs.data_ptr(), rp.data_ptr(), rv.data_ptr()], [0, 0, 0],
                                 he.SHD_MEM_DEVICE, co.astype(np.int64), True)
-                dq.discard()
+                if rows is None:
+                    dq.discard()
+                else:
+                    r = dq.poll()
+                    if r is not None:
+                        rows.append(r)
                 if collect is not None:
                     for k, v in dq.stage_times().items():
                         tot[k] = tot.get(k, 0) + v
@@ -934,8 +999,8 @@ def main():
 
         # SURVEY.md §8d algorithmic bytes need the reference's pending-scan counts
         # (P-bar: (partial, event) pairs its pending lists visit): the walks count
-        # exactly those, taken from one untimed calibration step.
-        calib = run_step() if pattern else None
+        # exactly those, taken from one untimed calibration step (--full).
+        calib = run_step() if pattern and args.full else None
         for _ in range(args.warmup):
             run_step()
         torch.cuda.synchronize()
@@ -957,6 +1022,21 @@ def main():
         ms_per_step = elapsed / args.steps * 1e3
         total_events = n * world * args.steps
         value = total_events / elapsed
+        if args.dump_outputs and dump:
+            # the last timed step once more, untimed: the same pushes from the
+            # same fresh state, polled where the timed loop drops the rows
+            # (the copy to the host stays out of ms_per_step); its counters
+            # must be the timed step's
+            parts = []
+            again = run_step(rows=parts)
+            same = ("events", "matches", "partials", "partial_scans", "carry")
+            if any(again[k] != counters[k] for k in same):
+                raise SystemExit("--dump-outputs: the polled step's counters %r differ from the last timed step's %r"
+                                 % ({k: again[k] for k in same}, {k: counters[k] for k in same}))
+            got, kept = dump_rows(args.dump_outputs, parts, qp.output_types, "_rank%d" % rank if world > 1 else "")
+            if rank == 0:
+                print("dump-outputs: %d of %d rows of one step -> %s" % (kept, got, args.dump_outputs),
+                      file=sys.stderr, flush=True)
         return dict(sym=sym, price=price, vol=vol, ts=ts, seqs=seqs, kb=kb, dq=dq, calib=calib, counters=counters,
                     halo=take[0],
                     stage_runs=stage_runs, elapsed=elapsed, ms_per_step=ms_per_step, value=value, batch=batch,
@@ -968,8 +1048,8 @@ def main():
                                                                         "ms_per_step", "value"))
     batch, offs_all, total_events = M["batch"], M["offs_all"], M["total_events"]
     alongside = None
-    if world > 1 and mode == "roundrobin" and args.input == "auto":
-        A = measure("prepartitioned")
+    if args.full and world > 1 and mode == "roundrobin" and args.input == "auto":
+        A = measure("prepartitioned", dump=False)
         A["dq"].close()
         alongside = {"input": "prepartitioned", "keys_per_gpu": keys, "value": round(A["value"], 1),
                      "ms_per_step": round(A["ms_per_step"], 3), "matches": A["counters"]["matches"] * world}
@@ -981,12 +1061,13 @@ def main():
         for k, v in r.items():
             stages[k] = stages.get(k, 0) + v / len(stage_runs)
     step_dev_ns = sum(stages.values())
-    if pattern:
+    bytes_step, derived = None, None
+    if args.full and pattern:
         bytes_step, derived = alg_bytes_pattern(calib, calib["events"])
-    else:
+    elif args.full:
         bytes_step, derived = alg_bytes_window(counters, counters["events"], len(qp.output_names))
     roof = None
-    if stages:
+    if stages and bytes_step is not None:
         # frac: the path's algorithmic bytes per step / the wall time of a step
         # (recomputable from this line: alg_bytes_per_event * events / ms_per_step);
         # device_*: / the HIP-event time of the push pipeline; kernels: each
@@ -1018,7 +1099,7 @@ def main():
     cpu_mt = None
     prefix = None
     derived_check = None
-    if rank == 0 and world == 1 and args.cpu_sample != 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample != 0:
         sample = args.cpu_sample if args.cpu_sample > 0 else (4_000_000 if pattern else 2_000_000)
         sample = min(sample, n)
         cpu, ora_rows, _, oc = cpu_baseline(args.config, app, keys, delta, sample)
@@ -1082,7 +1163,7 @@ def main():
                                                   "rank and step)" % M["halo"]}.get(mode, "")},
             "matches_per_s": round(matches_per_s, 1),
             "counters": {k: counters[k] for k in ("events", "matches", "partials", "partial_scans", "carry")},
-            "derived": {k: round(v, 4) for k, v in derived.items()},
+            "derived": {k: round(v, 4) for k, v in derived.items()} if derived is not None else None,
             "stage_ms_per_step": {k: round(v / 1e6, 3) for k, v in stages.items()},
             "roofline": roof,
             "cpu_baseline": cpu,
