@@ -38,6 +38,7 @@
 #include <cstdlib>
 
 #include "engine.h"
+#include "knobs.h"
 
 namespace shd {
 
@@ -2204,11 +2205,10 @@ struct GraphBuilder {
   }
 };
 
-int env_int(const char* name, int def) {
-  const char* v = std::getenv(name);
-  if (!v || !*v) return def;
-  int x = std::atoi(v);
-  return x > 0 ? x : def;
+// a per-key capacity knob: its value when positive, else the default
+int knob_capacity(Knob k, int def) {
+  int v;
+  return knob_int(k, v) && v > 0 ? v : def;
 }
 
 }  // namespace
@@ -2242,7 +2242,7 @@ struct NfaEngine : Engine {
   int64_t win_horizon = 0;   // patterns: longest within / for time (0: none)
   DevBuf d_hash;
   int64_t win_fallbacks = 0;   // window passes rerun with longer warm-ups
-  const bool win_debug = getenv("SHD_NFA_DEBUG") != nullptr;
+  const bool win_debug = knob_on(Knob::NFA_DEBUG);
   bool partitioned = false;
   int key_expr[kNStream], key_col[kNStream], key_type[kNStream];
   // key blocks
@@ -2871,7 +2871,7 @@ struct NfaEngine : Engine {
         // lanes of >= 32 events, enough of them to fill the chip, and a
         // warm-up of at most 4 chunks
         int64_t chunk = std::max<int64_t>({32, std::min<int64_t>(1024, n / 16384), ceil_div(warm, 4)});
-        if (const char* e = getenv("SHD_NFA_CHUNK")) chunk = std::max(1, atoi(e));
+        if (int v; knob_int(Knob::NFA_CHUNK, v)) chunk = std::max(1, v);
         const int64_t nl = ceil_div(n, chunk);
         const int64_t c0 = std::min<int64_t>(nl, warm / chunk + 1);   // lanes with ob <= warm
         ensure_slots(nl + 1);   // may move the key blocks
@@ -2879,7 +2879,7 @@ struct NfaEngine : Engine {
         d_hash.reserve(4 * nl * 8);
         ra.hash_w = d_hash.as<uint64_t>();
         ra.hash_e = d_hash.as<uint64_t>() + 2 * nl;
-        ra.hash1_zero = getenv("SHD_NFA_HASH1_ZERO") != nullptr;
+        ra.hash1_zero = knob_on(Knob::NFA_HASH1_ZERO);
         ra.chunk_len = chunk;
         ra.warm = warm;
         ra.c_exact = c0;
@@ -3044,7 +3044,7 @@ void layout_offsets(NfaLayout& Y) {
   // state contiguous (measured slower on window lanes too: S4-seq 158 vs 182 M
   // events/s, S4P-seqplus 190 vs 199 M)
   Y.W = kLaneBlock;
-  if (const char* w = getenv("SHD_NFA_INTERLEAVE")) Y.W = w[0] == '0' ? 1 : kLaneBlock;
+  if (knob_force(Knob::NFA_INTERLEAVE) == 0) Y.W = 1;
   const int64_t falign = Y.W == 1 ? 16 : 256;
   int64_t off = 0;
   Y.nf = 0;
@@ -3275,8 +3275,8 @@ std::unique_ptr<Engine> make_nfa_engine(const Plan& p, std::string& why, int64_t
     }
     if (absent_logical && !(p.state_type == 1)) horizon = 0;
     const bool seq = p.state_type == 1;
-    const char* wenv = getenv("SHD_NFA_WINDOW");
-    if (!e->partitioned && every_start && (seq || horizon > 0) && !(wenv && wenv[0] == '0') && list_hint == 0) {
+    if (!e->partitioned && every_start && (seq || horizon > 0) && knob_force(Knob::NFA_WINDOW) != 0 &&
+        list_hint == 0) {
       e->windowed = true;
       const int64_t sp = span(p.root);
       e->win_span = seq && sp > 0 ? sp : 0;
@@ -3299,11 +3299,11 @@ std::unique_ptr<Engine> make_nfa_engine(const Plan& p, std::string& why, int64_t
     while (L0 < 2 * list_hint && L0 < 32768) L0 *= 2;
     S0 = std::max(S0, std::min(2 * L0, 32768));
   }
-  Y.L = env_int("SHD_NFA_LIST", L0);
-  Y.SC = std::min(env_int("SHD_NFA_PARTIALS", S0), 32768);
-  Y.EC = std::min(env_int("SHD_NFA_EVENTS", 2 * Y.SC), 65000);
-  Y.RC = std::min(env_int("SHD_NFA_RECORDS", S0), 65000);
-  Y.QC = env_int("SHD_NFA_TIMERS", many ? 32 : 1024);
+  Y.L = knob_capacity(Knob::NFA_LIST, L0);
+  Y.SC = std::min(knob_capacity(Knob::NFA_PARTIALS, S0), 32768);
+  Y.EC = std::min(knob_capacity(Knob::NFA_EVENTS, 2 * Y.SC), 65000);
+  Y.RC = std::min(knob_capacity(Knob::NFA_RECORDS, S0), 65000);
+  Y.QC = knob_capacity(Knob::NFA_TIMERS, many ? 32 : 1024);
   Y.RETC = std::min(Y.L * std::max(npre, 1), 65000);
   Y.WK = 4 * kNP;
   if (Y.L >= 65000 || Y.QC >= 65000) {

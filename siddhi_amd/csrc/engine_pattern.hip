@@ -30,6 +30,7 @@
 #include <cstdlib>
 
 #include "engine.h"
+#include "knobs.h"
 #include "pattern_common.h"
 
 namespace shd {
@@ -1780,10 +1781,9 @@ struct PatternEngine : Engine {
   // span, E = n * (W+1) / (T+1) / 2^b, against the passes saved.
   // SHD_HASH_BITS=b forces b (tests), SHD_NO_HASH disables.
   int hashed_bucket_bits(const PrepAgg& pg, int64_t n_ext, int key_bits, bool prune) const {
-    if (getenv("SHD_NO_HASH")) return 0;
+    if (knob_on(Knob::NO_HASH)) return 0;
     if (!prune || pg.unmono || (C > 0 && pg.carry_tmax > pg.ts_min) || pg.ts_max < pg.ts_min) return 0;
-    if (const char* f = getenv("SHD_HASH_BITS")) {
-      const int b = atoi(f);
+    if (int b; knob_int(Knob::HASH_BITS, b)) {
       return b > 0 && b <= 32 ? b : 0;
     }
     const int exact_passes = (key_bits + 7) / 8;
@@ -1887,11 +1887,11 @@ struct PatternEngine : Engine {
     // fused prepare + first sort pass: partitioned on a 32-bit plain key
     // attribute, f1 pre-decoded over at most one attribute, a push big enough
     // to pay for the extra launches (SHD_FUSED_SORT=0 / 1: off / on at any size)
-    const char* fs_env = getenv("SHD_FUSED_SORT");
+    const int fs_force = knob_force(Knob::FUSED_SORT);
     const int fattr = keyed_sort_f1_attr(pa.f1, isA);
     const bool fused = partitioned && !key64 && pa.key_col >= 0 && fattr >= -1 &&
                        (key_type[slot] == SHD_T_STRING || key_type[slot] == SHD_T_INT) && n_ext >= 2 &&
-                       (fs_env ? atoi(fs_env) != 0 : n_ext >= ((int64_t)1 << 20));
+                       (fs_force >= 0 ? fs_force != 0 : n_ext >= ((int64_t)1 << 20));
     KsInfo* d_ksi = reinterpret_cast<KsInfo*>(d_agg.as<char>() + 232);
     if (fused) {
       // the key range (ev_pg) is all the remaining passes need; the pushed
@@ -2017,7 +2017,7 @@ struct PatternEngine : Engine {
       SHD_HIP(hipEventSynchronize(ev_pt));
       std::memcpy(&pg, h_agg.as<char>() + 256, sizeof(pg));
     }
-    if (pg.ovf || getenv("SHD_TS64")) {   // SHD_TS64: force the 64-bit path (tests)
+    if (pg.ovf || knob_on(Knob::TS64)) {   // SHD_TS64: force the 64-bit path (tests)
       // some timestamp is more than 2^31 ms away from the batch's first event
       d_ts64.reserve(n_ext * 8);
       hipLaunchKernelGGL(k_sorted_ts64, dim3(grid_cover(n_ext)), dim3(kBlock), 0, s, dev_args(x), spv, n_ext,
@@ -2067,24 +2067,24 @@ struct PatternEngine : Engine {
     // partial from the start (no capped lane phase: the operand state would
     // have to travel between the two passes)
     int rmode = dense ? (hash_mask ? 1 : (logical != 2 ? 3 : (and_indep ? 2 : 1))) : 0;
-    if (const char* f = getenv("SHD_RESUME_MODE")) {
-      const int m = atoi(f);
+    if (int m; knob_int(Knob::RESUME_MODE, m)) {
       if (m >= 0 && m <= 3 && !(m >= 2 && (hash_mask || (logical == 2 && (m == 3 || !and_indep))))) rmode = m;
     }
     // plain form over the full-key sort with a pre-decoded f2 and walks shorter
     // than the block-skip range: lockstep walks (k_lockstep_walk) instead of
     // the hot walk + deferred walks -- by default where the capped lane walks
     // would run (dense keys); SHD_LOCKSTEP=0 / 1 forces
-    const char* ls_env = getenv("SHD_LOCKSTEP");
+    const int ls_force = knob_force(Knob::LOCKSTEP);
     const bool lockstep = grouped && !hash_mask && !sorted64 && logical == 0 && isB && fast2 && e_key < 64.0 &&
-                          (ls_env ? atoi(ls_env) != 0 : rmode == 3);
+                          (ls_force >= 0 ? ls_force != 0 : rmode == 3);
     // dense grouped walks revisit each position once per partial of its key
     // inside `within`: the e2 attributes the filters read are copied into
     // position order once, so the walks load them coalesced; worth its pass
     // only when walks are long (SHD_NO_BPOS: off, SHD_BPOS: always when dense)
-    if (grouped && (rmode != 0 || lockstep) && isB && bpos_mask && !getenv("SHD_NO_BPOS") && (e_key >= 8.0 || getenv("SHD_BPOS"))) {
+    if (grouped && (rmode != 0 || lockstep) && isB && bpos_mask && !knob_on(Knob::NO_BPOS) &&
+        (e_key >= 8.0 || knob_on(Knob::BPOS))) {
       // e1 operands position-major too (same stream schema, columns the carry keeps)
-      uint32_t apos = getenv("SHD_NO_APOS") ? 0u : (apos_mask & carry_mask);
+      uint32_t apos = knob_on(Knob::NO_APOS) ? 0u : (apos_mask & carry_mask);
       for (int c = 0; c < kMaxCols; c++)
         if (((apos >> c) & 1u) && (c >= b.cs.ncols || c >= (int)typesA.size() || typesA[c] != b.cs.type[c]))
           apos &= ~(1u << c);
@@ -2104,12 +2104,12 @@ struct PatternEngine : Engine {
     }
     // plain form: f2 split per comparison (SHD_NO_SPLIT: eval_fpred per step)
     sa.sp = F2Split{};
-    if (fast2 && logical == 0 && !getenv("SHD_NO_SPLIT")) split_f2(sa.f2.fp, s_first, sa.x, sa.sp);
+    if (fast2 && logical == 0 && !knob_on(Knob::NO_SPLIT)) split_f2(sa.f2.fp, s_first, sa.x, sa.sp);
     // long dense walks (a partial expects >= 64 events of its key inside
     // `within`) skip whole 64-position blocks that cannot end them
     sa.bsum = nullptr;
     const bool skip_ok = grouped && !hash_mask && !sorted64 && !ts64 && isB && logical == 0 && rmode != 0 && !lockstep &&
-                         sa.f2.fp.ok && !getenv("SHD_NO_BLOCK_SKIP") && (e_key >= 64.0 || getenv("SHD_BLOCK_SKIP"));
+                         sa.f2.fp.ok && !knob_on(Knob::NO_BLOCK_SKIP) && (e_key >= 64.0 || knob_on(Knob::BLOCK_SKIP));
     if (skip_ok && block_skip_term(sa.f2.fp, s_first, sa.bs_ci, sa.bs_side, sa.bs_op, sa.bs_attr)) {
       d_bsum.reserve(ceil_div(n_ext, 64) * (int64_t)sizeof(BlockSum));
       sa.bsum = d_bsum.as<BlockSum>();
@@ -2117,7 +2117,7 @@ struct PatternEngine : Engine {
     const ScanArgs* d_sa = dev_args(sa);
     // sparse keys (MODE 0): the deferred walks from a compacted list
     // (k_resume_list) unless SHD_NO_RESUME_LIST
-    const bool rlist = rmode == 0 && !lockstep && !sa.bsum && !sorted64 && !getenv("SHD_NO_RESUME_LIST");
+    const bool rlist = rmode == 0 && !lockstep && !sa.bsum && !sorted64 && !knob_on(Knob::NO_RESUME_LIST);
     const int nlb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, ceil_div(n_ext, (int64_t)64 * kBlock)));
     if (sa.bsum) {
       hipLaunchKernelGGL(k_block_sum, dim3(grid_for(ceil_div(n_ext, 64) * 64, 1, 4096)), dim3(kBlock), 0, s, d_sa,
@@ -2349,9 +2349,9 @@ struct PatternEngine : Engine {
         skey32 = d_k32.as<uint32_t>();
         skey64 = d_k64.as<uint64_t>();
       }
-      if (logical != 2 && !getenv("SHD_CARRY_SERIAL")) {
+      if (logical != 2 && !knob_on(Knob::CARRY_SERIAL)) {
         ga.amask = carry_mask;
-        if (grouped && !getenv("SHD_GATHER_ROWS")) {
+        if (grouped && !knob_on(Knob::GATHER_ROWS)) {
           ga.sts32 = fin_sts32;
           ga.sts64 = fin_sts64;
           // the partition key attribute of stream A, a 32-bit plain column (sorted key == its value)
@@ -2642,7 +2642,7 @@ std::unique_ptr<Engine> finish_pattern_engine(const Plan& p, const PNode& a, con
   }
   for (auto& o : p.outputs) e->outs.push_back(o.second);
   e->partitioned = !p.part_keys.empty();
-  if (!e->partitioned && !c && !getenv("SHD_NO_IMPLICIT_KEY")) {
+  if (!e->partitioned && !c && !knob_on(Knob::NO_IMPLICIT_KEY)) {
     int aa, ab, t;
     // one stream playing both roles: an event has one key, so both sides must be the same attribute
     if (find_key_equality(p, b.filters, aa, ab, t) && (a.stream != b.stream || aa == ab)) {

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "engine.h"
+#include "knobs.h"
 #include "gdict.h"
 #include "agg.h"
 
@@ -2913,11 +2914,11 @@ struct SingleEngine : Engine {
     }
     // aggregate queries (never inside a partition here: those run on the
     // keyed window engine) filter and build their items in one pass
-    if (agg_mode && !partitioned && !getenv("SHD_NO_FUSED_ITEMS")) {
+    if (agg_mode && !partitioned && !knob_on(Knob::NO_FUSED_ITEMS)) {
       push_agg_fused(b, ncalls, n, fa);
     } else {
       const FilterArgs* d_fa = dev_args(fa);
-      if (std::getenv("SHD_DEBUG_ARGS")) debug_filter_args(d_fa, fa, n);
+      if (knob_on(Knob::DEBUG_ARGS)) debug_filter_args(d_fa, fa, n);
       hipLaunchKernelGGL(k_filter, dim3(grid_cover(n)), dim3(kBlock), 0, s, d_fa, n, d_flags.as<uint8_t>(),
                          d_cnt.as<uint32_t>(), d_pkey.as<uint64_t>());
       SHD_CHECK_LAUNCH();
@@ -3101,7 +3102,7 @@ struct SingleEngine : Engine {
         ea.okind[c] = 2;
         ea.oarg[c] = code[0].a;
       }
-      if (getenv("SHD_NO_FAST_OUT")) ea.okind[c] = 0;
+      if (knob_on(Knob::NO_FAST_OUT)) ea.okind[c] = 0;
     }
     ea.nagg = nagg;
     for (int g = 0; g < nagg; g++) ea.kind[g] = plan.aggs[g].kind;
@@ -3141,7 +3142,7 @@ struct SingleEngine : Engine {
     snn.reserve(total);
     se.reserve(total * 4);
     scall.reserve(total * 4);
-    if (NC <= 2 && !getenv("SHD_SEG_UNPACKED")) {
+    if (NC <= 2 && !knob_on(Knob::SEG_UNPACKED)) {
       constexpr int N2 = NC <= 2 ? NC : 1;
       // packed in item order (coalesced), then one record read per sorted position
       seg_items.reserve((size_t)total * sizeof(SegItem<N2>));
@@ -3165,7 +3166,7 @@ struct SingleEngine : Engine {
     tagg.reserve(nt * sizeof(SegAcc<NC>));
     segS.reserve((size_t)NC * total * sizeof(DD));
     segNN.reserve((size_t)NC * total * 4);
-    const bool lds = NC <= 2 && !getenv("SHD_SEG_NOLDS");
+    const bool lds = NC <= 2 && !knob_on(Knob::SEG_NOLDS);
     if (lds)
       hipLaunchKernelGGL(k_seg_tiles_lds<(NC <= 2 ? NC : 1)>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
                          (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(),
@@ -3282,7 +3283,7 @@ struct SingleEngine : Engine {
     // opt-in (SHD_WCHUNK=1): on W2 the per-chunk workgroups (144 KB of LDS:
     // one per CU) are latency-bound -- r03m: 13.5 ms of delta + emit per
     // 100 M events against 10.4 ms for the group sort + segmented scans
-    if (!getenv("SHD_WCHUNK") || getenv("SHD_NO_WCHUNK") || ngk == 0 || (wkind != SHD_W_LENGTH && wkind != SHD_W_TIME) ||
+    if (!knob_on(Knob::WCHUNK) || knob_on(Knob::NO_WCHUNK) || ngk == 0 || (wkind != SHD_W_LENGTH && wkind != SHD_W_TIME) ||
         nch > 2 ||
         kmax + 1 > (uint64_t)kWcMaxG || kmax + 1 < 64 || total >= (int64_t)INT32_MAX)
       return false;
@@ -3303,7 +3304,7 @@ struct SingleEngine : Engine {
   DevBuf d_cw_citem, d_cw_clb;
   bool callwin_candidate(int64_t ncalls, int64_t total) const {
     if (!seg_mode || ngk == 0 || partitioned || nch > kMaxChan || (wkind != SHD_W_LENGTH && wkind != SHD_W_TIME) ||
-        total >= (int64_t)UINT32_MAX - 1 || ncalls <= 0 || getenv("SHD_NO_CALLWIN"))
+        total >= (int64_t)UINT32_MAX - 1 || ncalls <= 0 || knob_on(Knob::NO_CALLWIN))
       return false;
     for (size_t c = 0; c + 1 < h_offs.size(); c++)
       if (h_offs[c + 1] - h_offs[c] > kCwCall) return false;
@@ -3424,7 +3425,7 @@ struct SingleEngine : Engine {
     ca.status = d_cw_status.as<uint64_t>();
     ca.nrows = d_tot.as<uint64_t>() + 9;
     const CwArgs* d_ca = dev_args(ca);
-    if (kmax < (uint64_t)kCwDirectG && !getenv("SHD_CW_HASH")) {
+    if (kmax < (uint64_t)kCwDirectG && !knob_on(Knob::CW_HASH)) {
       // rows per call (distinct groups) -> each call's first row
       if (count_rows) {
         d_cw_cnt.reserve((size_t)ncalls * 4);
@@ -3593,7 +3594,7 @@ struct SingleEngine : Engine {
       ia.arg_col[g] = -1;
       if (ia.has_arg[g]) {
         ia.agg_arg[g] = dexpr(plan.aggs[g].expr);
-        if (!getenv("SHD_NO_FAST_OUT")) ia.arg_col[g] = plain_load_attr(plan, plan.aggs[g].expr);
+        if (!knob_on(Knob::NO_FAST_OUT)) ia.arg_col[g] = plain_load_attr(plan, plan.aggs[g].expr);
       }
     }
     ia.ngroup = ngk;
@@ -3821,7 +3822,7 @@ struct SingleEngine : Engine {
         throw NeedDissolve("query group: a call above 1024 events or a window beyond the call-window path");
       // direct-mapped group ids: one rows kernel for all members (they share
       // the calls' row counts); hashed ids: a launch per member
-      const bool multi = kmax < (uint64_t)kCwDirectG && !getenv("SHD_CW_HASH") && !getenv("SHD_CW_NO_MULTI") &&
+      const bool multi = kmax < (uint64_t)kCwDirectG && !knob_on(Knob::CW_HASH) && !knob_on(Knob::CW_NO_MULTI) &&
                          wkind == SHD_W_LENGTH;
       std::vector<const CwArgs*> margs;
       int mnch = 1;
@@ -3915,14 +3916,14 @@ struct SingleEngine : Engine {
       const FoldArgs* d_fo = dev_args(fo);
       // long group segments: one wave per group (coalesced operand loads,
       // wave-uniform fold); short ones: one lane per group
-      const bool wave = nops >= 256 * nheads && !getenv("SHD_FOLD_LANE");
+      const bool wave = nops >= 256 * nheads && !knob_on(Knob::FOLD_LANE);
 #define SHD_FOLD_ARGS                                                                                           \
   d_fo, (const uint32_t*)hlist.as<uint32_t>(), nheads, nops, sk, sr, (const uint64_t*)iargv[cur].as<uint64_t>(), \
       (const uint8_t*)iargn[cur].as<uint8_t>(), (const int32_t*)ievrow.as<int32_t>(),                            \
       (const int32_t*)d_call_of.as<int32_t>(), resv.as<uint64_t>(), resn.as<uint8_t>(), resc.as<int64_t>(),     \
       first.as<uint8_t>(), last_of.as<uint32_t>()
       // aggregators with a double running sum + count only: the branch-light fold
-      bool dfam = nagg >= 1 && nagg <= 4 && !getenv("SHD_FOLD_GENERIC");
+      bool dfam = nagg >= 1 && nagg <= 4 && !knob_on(Knob::FOLD_GENERIC);
       for (int g = 0; g < nagg; g++) {
         const int k = plan.aggs[g].kind, t = plan.aggs[g].type;
         dfam = dfam && (k == SHD_AGG_COUNT || k == SHD_AGG_AVG ||
@@ -4043,7 +4044,7 @@ std::unique_ptr<Engine> make_single_engine(const Plan& p, std::string& why) {
     e->chan_of[g] = c;
   }
   e->seg_ok = seg;
-  e->seg_pref = !getenv("SHD_EXACT_AGGREGATES");
+  e->seg_pref = !knob_on(Knob::EXACT_AGGREGATES);
   e->seg_mode = seg && e->seg_pref;
   if (e->partitioned) {
     e->key_expr = p.part_keys[0].second;
@@ -4060,7 +4061,7 @@ std::unique_ptr<Engine> make_single_engine(const Plan& p, std::string& why) {
   // dense ids: one string attribute (dictionary ids; null = the id of "null")
   // or one bool attribute (0, 1, null = 2); the group dictionary otherwise
   e->gdense = e->ngk == 1 && ((e->gk_type[0] == SHD_T_STRING && p.null_str_id >= 0) || e->gk_type[0] == SHD_T_BOOL);
-  if (getenv("SHD_GROUP_DICT")) e->gdense = false;   // tests: dictionary path for every key
+  if (knob_on(Knob::GROUP_DICT)) e->gdense = false;   // tests: dictionary path for every key
   return e;
 }
 

@@ -41,6 +41,7 @@
 #include <type_traits>
 
 #include "engine.h"
+#include "knobs.h"
 #include "radix_tile.h"
 #include "pattern_common.h"
 
@@ -722,7 +723,7 @@ void keyed_sort_pass0(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, i
   const bool knul = pa.x.batch.nul[pa.key_col] != nullptr;
   const bool fnul = fattr >= 0 && pa.x.batch.nul[fattr] != nullptr;
   const int fsz = fattr >= 0 ? type_size(pa.x.batch.type[fattr]) : 0;
-  const KsF1 f1 = getenv("SHD_KS_GENERIC_F1") ? KsF1{} : ks_f1(pa.f1, pa.is_a ? fattr : -1, pa.x.batch);
+  const KsF1 f1 = knob_on(Knob::KS_GENERIC_F1) ? KsF1{} : ks_f1(pa.f1, pa.is_a ? fattr : -1, pa.x.batch);
   const int nb = k.nb;
   const uint32_t* hraw = k.hraw;
   const uint32_t* offs = k.offs;

@@ -7,6 +7,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "knobs.h"
 #include "radix_tile.h"
 
 namespace shd {
@@ -263,7 +264,7 @@ static void radix_sort_run(K* keys, uint32_t* vals, uint32_t* w, K* keys_alt, ui
   uint32_t* hist = scratch.as<uint32_t>();
   uint32_t* offs = hist + nh;
   uint32_t* dtot = offs + nh;
-  const int xcd = getenv("SHD_RS_NOXCD") ? 0 : 1;   // A/B switch for the tile order
+  const int xcd = knob_on(Knob::RS_NOXCD) ? 0 : 1;   // A/B switch for the tile order
   K* ki = keys; uint32_t* vi = vals; uint32_t* wi = w;
   K* ko = keys_alt; uint32_t* vo = vals_alt; uint32_t* wo = w_alt;
   for (int shift = shift0; shift < bits; shift += 8) {

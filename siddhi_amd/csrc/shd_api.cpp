@@ -5,14 +5,12 @@
 #include <mutex>
 
 #include "engine.h"
+#include "knobs.h"
 
 namespace shd {
 
 void check_launch(const char* file, int line) {
-  static const bool sync = [] {
-    const char* v = std::getenv("SHD_SYNC_CHECK");
-    return v && *v && *v != '0';
-  }();
+  static const bool sync = knob_on(Knob::SYNC_CHECK);
   hipError_t e = hipGetLastError();
   if (e == hipSuccess && sync) e = hipDeviceSynchronize();
   if (e != hipSuccess)
@@ -487,8 +485,7 @@ DFilters Engine::dfilters(const std::vector<int>& ids) const {
   f.n = (int)ids.size();
   if (f.n > 4) throw Error(SHD_E_UNSUPPORTED, "more than 4 filters on one state");
   for (int i = 0; i < f.n; i++) f.f[i] = dexpr(ids[i]);
-  const char* nf = std::getenv("SHD_NO_FAST_PRED");   // interpreter only (cross-check in tests)
-  const bool no_fast = nf && *nf && *nf != '0';
+  const bool no_fast = knob_on(Knob::NO_FAST_PRED);   // interpreter only (cross-check in tests)
   if (no_fast || !compile_fast_pred(plan, ids, f.fp)) f.fp.ok = 0;
   return f;
 }
@@ -497,8 +494,7 @@ bool Engine::fast_atom(int expr_id, FAtom& out) const {
   out = FAtom{};
   out.kind = FA_NONE;
   out.cvt_from = out.cvt_to = -1;
-  const char* nf = std::getenv("SHD_NO_FAST_PRED");
-  if ((nf && *nf && *nf != '0') || expr_id < 0 || expr_id >= (int)plan.exprs.size()) return false;
+  if (knob_on(Knob::NO_FAST_PRED) || expr_id < 0 || expr_id >= (int)plan.exprs.size()) return false;
   const std::vector<Instr>& code = plan.exprs[expr_id];
   if (code.empty() || code.size() > 2) return false;
   const Instr& in = code[0];
@@ -901,11 +897,11 @@ int shd_plan_load(shd_ctx* ctx, const void* ir, size_t len, shd_query** out) {
       // the 2-state every-pattern shape (P1/P3) has a dedicated forward-scan
       // engine; every other state plan runs on the generic per-key NFA
       // SHD_FORCE_NFA: the generic engine for every state plan (tests, diagnostics)
-      if (!getenv("SHD_FORCE_NFA")) e = make_pattern_engine(p, why1);
+      if (!knob_on(Knob::FORCE_NFA)) e = make_pattern_engine(p, why1);
       // SHD_NO_LOGICAL_SCAN: leave `every e1 -> (e2 or e3)` to the generic NFA engine (tests)
-      if (!e && !getenv("SHD_NO_LOGICAL_SCAN") && !getenv("SHD_FORCE_NFA")) e = make_logical_pattern_engine(p, why1);
+      if (!e && !knob_on(Knob::NO_LOGICAL_SCAN) && !knob_on(Knob::FORCE_NFA)) e = make_logical_pattern_engine(p, why1);
       // SHD_NO_ABSENT_SCAN: leave `every e1 -> not X for t` to the generic NFA engine (tests)
-      if (!e && !getenv("SHD_NO_ABSENT_SCAN") && !getenv("SHD_FORCE_NFA")) e = make_absent_engine(p, why1);
+      if (!e && !knob_on(Knob::NO_ABSENT_SCAN) && !knob_on(Knob::FORCE_NFA)) e = make_absent_engine(p, why1);
       if (!e) e = make_nfa_engine(p, why2);
       if (!e) why1 += "; ";
     } else {
