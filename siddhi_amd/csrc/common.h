@@ -2,11 +2,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/siddhi_hip.h"
@@ -99,6 +101,44 @@ struct PinnedBuf {
     cap = b;
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A per-push readback block: the totals, maxima and flags an engine's kernels
+// and the library scans write (struct T, the device layout), paired with the
+// pinned host image the push decides from.  H is T, or a struct derived from
+// T that adds host-only fields.  Spans are named by their first and last
+// member; nothing here synchronises -- callers wait on their stream or event.
+template <class T, class H = T>
+struct ReadbackBlock {
+  static_assert(std::is_base_of<T, H>::value && std::is_trivially_copyable<H>::value, "host image extends T");
+  DevBuf d;
+  PinnedBuf h;
+  void reserve() {
+    d.reserve(sizeof(T));
+    h.reserve(sizeof(H));
+  }
+  T* dev() const { return d.as<T>(); }
+  H& host() const { return *h.as<H>(); }
+  template <class A> size_t offset_of(A T::*m) const {
+    const T& t = host();
+    return (size_t)(reinterpret_cast<const char*>(&(t.*m)) - reinterpret_cast<const char*>(&t));
+  }
+  // bytes of the members first .. last (inclusive)
+  template <class A, class B> size_t span(A T::*first, B T::*last) const {
+    return offset_of(last) + sizeof(B) - offset_of(first);
+  }
+  // one device -> host copy of the members first .. last
+  template <class A, class B> void fetch(A T::*first, B T::*last, hipStream_t s) {
+    const size_t o = offset_of(first);
+    SHD_HIP(hipMemcpyAsync(reinterpret_cast<char*>(static_cast<T*>(&host())) + o, d.as<char>() + o, span(first, last),
+                           hipMemcpyDeviceToHost, s));
+  }
+  template <class A> void fetch(A T::*m, hipStream_t s) { fetch(m, m, s); }
+  // one device memset of the members first .. last
+  template <class A, class B> void clear(A T::*first, B T::*last, int byte, hipStream_t s) {
+    SHD_HIP(hipMemsetAsync(d.as<char>() + offset_of(first), byte, span(first, last), s));
+  }
+  template <class A> void clear(A T::*m, int byte, hipStream_t s) { clear(m, m, byte, s); }
 };
 
 // ------------------------------------------------------------------ plan (host decode)

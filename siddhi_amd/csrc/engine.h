@@ -245,6 +245,23 @@ struct Engine {
     return reinterpret_cast<const T*>(arg_dev.as<char>() + off);
   }
 
+  // One u32 read back on the engine's stream: 4 bytes from `dev` into the
+  // pinned word `pinned`, then a stream synchronise.
+  uint32_t read_u32(const void* dev, uint32_t* pinned) {
+    SHD_HIP(hipMemcpyAsync(pinned, dev, 4, hipMemcpyDeviceToHost, stream));
+    SHD_HIP(hipStreamSynchronize(stream));
+    return *pinned;
+  }
+  // Exclusive scan that returns its total.  The scan leaves the total in
+  // *total_dev (a field of the engine's readback block, `total_pinned` the
+  // same field of its host image).  Not for totals read back with others.
+  uint32_t scan(const uint32_t* in, uint32_t* outp, int64_t n, uint32_t* total_dev, uint32_t* total_pinned,
+                DevBuf& scratch) {
+    if (n <= 0) return 0;
+    scan_exclusive_u32(in, outp, n, total_dev, scratch, stream);
+    return read_u32(total_dev, total_pinned);
+  }
+
   DExpr dexpr(int e) const { return DExpr{ex.off[e], ex.len[e]}; }
   DExprSet dset() const { return DExprSet{ex.ins.as<int4>(), ex.consts.as<uint64_t>(), ex.nins, ex.nconsts}; }
   DFilters dfilters(const std::vector<int>& ids) const;

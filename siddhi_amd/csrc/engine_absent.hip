@@ -54,6 +54,21 @@ struct AbsOut {
   unsigned int pad;
 };
 
+// The absent engine's per-push readback block (AbsentEngine::agg).
+struct AbsentTotals {
+  union {
+    AbsOut out;                 // k_abs_fold (push)
+    unsigned long long n_due;   // k_abs_due (set_time: no push is in flight then)
+  };
+  uint64_t pad_;
+  uint32_t n_fired;   // scan_exclusive_u32: partials that fired
+  uint32_t n_open;    // scan_exclusive_u32: partials still open
+};
+static_assert(offsetof(AbsentTotals, out) == 0 && offsetof(AbsentTotals, n_due) == 0 &&
+                  offsetof(AbsentTotals, n_fired) == 32 && offsetof(AbsentTotals, n_open) == 36 &&
+                  sizeof(AbsentTotals) <= 64,
+              "AbsentTotals device layout");
+
 __device__ __forceinline__ int first_off_after(const AbsArgs& a, int64_t b) {
   int lo = 0, hi = a.ne;   // first e with e_off[e] > b
   while (lo < hi) {
@@ -351,8 +366,9 @@ struct AbsentEngine : Engine {
   AbsTable carry[2];
   int cur = 0;
   int64_t C = 0;
-  DevBuf d_st, d_fe, d_bcnt, d_boff, d_blk, d_agg, d_list, d_scan, d_eoff, d_enow, d_ends, d_last;
-  PinnedBuf h_agg, h_last;
+  DevBuf d_st, d_fe, d_bcnt, d_boff, d_blk, d_list, d_scan, d_eoff, d_enow, d_ends, d_last;
+  PinnedBuf h_last;
+  ReadbackBlock<AbsentTotals> agg;
 
   int kind() const override { return ENG_PATTERN; }
 
@@ -428,14 +444,13 @@ struct AbsentEngine : Engine {
     if (t < now) return;
     now = t;
     if (C == 0) return;
-    d_agg.reserve(64);
-    h_agg.reserve(64);
+    agg.reserve();
     hipLaunchKernelGGL(k_abs_due, dim3(1), dim3(kBlock), 0, stream, carry[cur].ts.as<int64_t>(), C, T, t,
-                       d_agg.as<unsigned long long>());
+                       &agg.dev()->n_due);
     SHD_CHECK_LAUNCH();
-    SHD_HIP(hipMemcpyAsync(h_agg.p, d_agg.p, 8, hipMemcpyDeviceToHost, stream));
+    agg.fetch(&AbsentTotals::n_due, stream);
     SHD_HIP(hipStreamSynchronize(stream));
-    const int64_t f = (int64_t)h_agg.as<unsigned long long>()[0];
+    const int64_t f = (int64_t)agg.host().n_due;
     if (f == 0) return;
     const ExtRows x = ext(nullptr);
     project(x, nullptr, f, nullptr, nullptr, seq);
@@ -503,8 +518,7 @@ struct AbsentEngine : Engine {
     d_bcnt.reserve((size_t)2 * ntile * 4);
     d_boff.reserve((size_t)2 * ntile * 4);
     d_blk.reserve((size_t)ntile * sizeof(AbsOut));
-    d_agg.reserve(64);
-    h_agg.reserve(64);
+    agg.reserve();
     const AbsArgs* d_aa = dev_args(aa);
     if (aa.f1.fp.ok && aa.fx.fp.ok)
       hipLaunchKernelGGL(k_abs_scan<true>, dim3(ntile), dim3(kBlock), 0, s, d_aa, n_ext, d_st.as<uint8_t>(),
@@ -514,17 +528,16 @@ struct AbsentEngine : Engine {
                          d_fe.as<int32_t>(), d_bcnt.as<uint32_t>(), d_blk.as<AbsOut>(), tile);
     SHD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_abs_fold, dim3(1), dim3(kBlock), 0, s, (const AbsOut*)d_blk.as<AbsOut>(), ntile,
-                       d_agg.as<AbsOut>());
+                       &agg.dev()->out);
     SHD_CHECK_LAUNCH();
-    uint32_t* d_tot = reinterpret_cast<uint32_t*>(d_agg.as<char>() + 32);
-    scan_exclusive_u32(d_bcnt.as<uint32_t>(), d_boff.as<uint32_t>(), ntile, d_tot, d_scan, s);
-    scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, d_tot + 1, d_scan, s);
-    SHD_HIP(hipMemcpyAsync(h_agg.p, d_agg.p, 40, hipMemcpyDeviceToHost, s));
+    scan_exclusive_u32(d_bcnt.as<uint32_t>(), d_boff.as<uint32_t>(), ntile, &agg.dev()->n_fired, d_scan, s);
+    scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, &agg.dev()->n_open, d_scan,
+                       s);
+    agg.fetch(&AbsentTotals::out, &AbsentTotals::n_open, s);
     SHD_HIP(hipStreamSynchronize(s));
     mark("absent_scan");
-    AbsOut so;
-    std::memcpy(&so, h_agg.p, sizeof(so));
-    const uint32_t n_fired = h_agg.as<uint32_t>()[8], n_open = h_agg.as<uint32_t>()[9];
+    const AbsOut so = agg.host().out;
+    const uint32_t n_fired = agg.host().n_fired, n_open = agg.host().n_open;
     if (so.unmono)   // emission order is the creation order only for time-ordered rows
       throw NeedNfa("absent pattern engine: event timestamps decrease");
     d_list.reserve((size_t)std::max<uint32_t>(std::max(n_fired, n_open), 1) * 4);

@@ -133,6 +133,13 @@ struct NfaCtl {
   unsigned int count;   // scan totals / slot counter
   unsigned long long lrows;   // list arena entries written (multi-value outputs)
 };
+// Pinned host side of the control block: its image (read_ctl) and the single
+// values other readbacks deliver, each in a field of its own.
+struct NfaCtlHost {
+  NfaCtl ctl;
+  uint32_t last_pos, last_head;   // order_rows: the last row's tag position / head flag
+  int64_t last_now;               // the last call's time (d_now)
+};
 
 struct NfaRunArgs {
   ColSet batch;
@@ -2379,11 +2386,9 @@ struct NfaEngine : Engine {
   }
 
   NfaCtl read_ctl() {
-    SHD_HIP(hipMemcpyAsync(h_ctl.p, d_ctl.p, sizeof(NfaCtl), hipMemcpyDeviceToHost, stream));
+    SHD_HIP(hipMemcpyAsync(&h_ctl.as<NfaCtlHost>()->ctl, d_ctl.p, sizeof(NfaCtl), hipMemcpyDeviceToHost, stream));
     SHD_HIP(hipStreamSynchronize(stream));
-    NfaCtl c;
-    std::memcpy(&c, h_ctl.p, sizeof(c));
-    return c;
+    return h_ctl.as<NfaCtlHost>()->ctl;
   }
 
   void ensure_slots(int64_t need) {
@@ -2765,7 +2770,7 @@ struct NfaEngine : Engine {
     d_first.reserve(ncalls * 8);
     d_run.reserve(n1 * 4);
     d_ctl.reserve(sizeof(NfaCtl));
-    h_ctl.reserve(256);
+    h_ctl.reserve(sizeof(NfaCtlHost));
     upload(d_offs.p, offs.data(), (ncalls + 1) * 8);
     if (b) {
       hipLaunchKernelGGL(k_nfa_calls, dim3(std::min(ncalls, 4096)), dim3(kBlock), 0, s,
@@ -2947,9 +2952,10 @@ struct NfaEngine : Engine {
     SHD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
     // host mirror of the playback clock: the last call's time
     int64_t last = now;
-    SHD_HIP(hipMemcpyAsync(h_ctl.as<char>() + 128, d_now.as<int64_t>() + (ncalls - 1), 8, hipMemcpyDeviceToHost, s));
+    SHD_HIP(hipMemcpyAsync(&h_ctl.as<NfaCtlHost>()->last_now, d_now.as<int64_t>() + (ncalls - 1), 8,
+                           hipMemcpyDeviceToHost, s));
     SHD_HIP(hipStreamSynchronize(s));
-    std::memcpy(&last, h_ctl.as<char>() + 128, 8);
+    last = h_ctl.as<NfaCtlHost>()->last_now;
     if (last > now) now = last;
     if (b) {
       seq += n;
@@ -3021,13 +3027,11 @@ struct NfaEngine : Engine {
                        out.d_nulls(), out.d_seq(), out.d_sidx(), prog.multi_mask, lbase);
     SHD_CHECK_LAUNCH();
     // chunk ids consumed = number of distinct tags
-    SHD_HIP(hipMemcpyAsync(h_ctl.as<char>() + 64, d_thpos.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, s));
-    SHD_HIP(hipMemcpyAsync(h_ctl.as<char>() + 68, d_thead.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, s));
+    NfaCtlHost& h = *h_ctl.as<NfaCtlHost>();
+    SHD_HIP(hipMemcpyAsync(&h.last_pos, d_thpos.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, s));
+    SHD_HIP(hipMemcpyAsync(&h.last_head, d_thead.as<uint32_t>() + (m - 1), 4, hipMemcpyDeviceToHost, s));
     SHD_HIP(hipStreamSynchronize(s));
-    uint32_t last_pos = 0, last_head = 0;
-    std::memcpy(&last_pos, h_ctl.as<char>() + 64, 4);
-    std::memcpy(&last_head, h_ctl.as<char>() + 68, 4);
-    chunk_seq += (int64_t)last_pos + last_head;
+    chunk_seq += (int64_t)h.last_pos + h.last_head;
     out.count += m;
     mark("order");
   }

@@ -122,9 +122,6 @@ __global__ __launch_bounds__(kBlock) void k_sorted_ts64(const ExtRows* __restric
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p = n) sts64[p] = x.ts(pv_row(spv[p]));
 }
 
-// d_agg layout: PrepAgg at 0, ScanOut at 64, match / open totals at 128
-static_assert(sizeof(PrepAgg) <= 64 && sizeof(ScanOut) <= 64, "d_agg layout");
-
 #include "pattern_walk.h"
 
 // Per-block reduction of the scan counters: ScanOut partial at blk[slot] and
@@ -1575,11 +1572,11 @@ struct PatternEngine : Engine {
   const int64_t* fin_sts64 = nullptr;
   // scratch
   DevBuf d_k32, d_k32_alt, d_k64, d_k64_alt, d_pv, d_pv_alt, d_ts, d_ts_alt, d_ts64, d_match, d_pst, d_bcnt, d_boff, d_pj,
-      d_pi, d_pj_alt, d_pi_alt, d_agg, d_sort, d_scan, d_blk, d_mother, d_se1, d_sot, d_olist, d_dlist;
+      d_pi, d_pj_alt, d_pi_alt, d_sort, d_scan, d_blk, d_mother, d_se1, d_sot, d_olist, d_dlist;
   // stream-A attributes read again after a partial is carried (state-0 loads
   // of f2 / f3 / the selector): only these columns are copied into the carry
   uint32_t carry_mask = ~0u;
-  PinnedBuf h_agg;
+  ReadbackBlock<PatternTotals, PatternTotalsHost> agg;   // per-push totals (pattern_common.h)
 
   int kind() const override { return ENG_PATTERN; }
 
@@ -1838,8 +1835,7 @@ struct PatternEngine : Engine {
     }
     d_match.reserve(n_ext * 4);
     d_pst.reserve(n_ext + kCompactPad);
-    d_agg.reserve(256);
-    h_agg.reserve(320);
+    agg.reserve();
 
     ExtRows x{};
     x.carry = carry_cs();
@@ -1872,11 +1868,13 @@ struct PatternEngine : Engine {
     }
     pa.carry_key = carry[cur].key.as<uint64_t>();
     PrepAgg init{0, 0, LLONG_MAX, LLONG_MIN, 0, 0, LLONG_MIN, ULLONG_MAX};
-    PrepAgg* d_pa = d_agg.as<PrepAgg>();
-    ScanOut* d_so = reinterpret_cast<ScanOut*>(d_agg.as<char>() + 64);
-    std::memcpy(h_agg.p, &init, sizeof(init));
-    std::memset(h_agg.as<char>() + 64, 0, sizeof(ScanOut));
-    SHD_HIP(hipMemcpyAsync(d_agg.p, h_agg.p, 128, hipMemcpyHostToDevice, s));
+    PatternTotalsHost& h_agg = agg.host();
+    PrepAgg* d_pa = &agg.dev()->prep;
+    ScanOut* d_so = &agg.dev()->scan;
+    h_agg.prep = init;
+    h_agg.scan = ScanOut{};
+    // the prepare and scan slots, up to the first scan total
+    SHD_HIP(hipMemcpyAsync(agg.dev(), &h_agg, offsetof(PatternTotals, n_match), hipMemcpyHostToDevice, s));
     // 4096 workgroups (16 waves per SIMD at full occupancy): enough to stream
     // at full bandwidth, and the one-block folds of the per-block partials
     // (k_finish_prep / k_finish_scan) stay short
@@ -1892,19 +1890,19 @@ struct PatternEngine : Engine {
     const bool fused = partitioned && !key64 && pa.key_col >= 0 && fattr >= -1 &&
                        (key_type[slot] == SHD_T_STRING || key_type[slot] == SHD_T_INT) && n_ext >= 2 &&
                        (fs_force >= 0 ? fs_force != 0 : n_ext >= ((int64_t)1 << 20));
-    KsInfo* d_ksi = reinterpret_cast<KsInfo*>(d_agg.as<char>() + 232);
+    KsInfo* d_ksi = &agg.dev()->ks;
     if (fused) {
       // the key range (ev_pg) is all the remaining passes need; the pushed
       // rows' time aggregates and the candidate count arrive with the first
-      // pass (ev_pt, into h_agg + 256), read while the remaining passes run
+      // pass (ev_pt, into prep_pass0), read while the remaining passes run
       if (!ev_pg) SHD_HIP(hipEventCreateWithFlags(&ev_pg, hipEventDisableTiming));
       if (!ev_pt) SHD_HIP(hipEventCreateWithFlags(&ev_pt, hipEventDisableTiming));
       keyed_sort_front(s, d_pa_args, pa, n_ext, d_kps, d_pa, d_ksi);
-      SHD_HIP(hipMemcpyAsync(h_agg.p, d_agg.p, 64, hipMemcpyDeviceToHost, s));
+      agg.fetch(&PatternTotals::prep, s);
       SHD_HIP(hipEventRecord(ev_pg, s));
       keyed_sort_pass0(s, d_pa_args, pa, fattr, n_ext, d_kps, d_ksi, d_k32.as<uint32_t>(), d_pv.as<uint32_t>(),
                        d_ts.as<uint32_t>(), d_pa);
-      SHD_HIP(hipMemcpyAsync(h_agg.as<char>() + 256, d_agg.p, 64, hipMemcpyDeviceToHost, s));
+      SHD_HIP(hipMemcpyAsync(&h_agg.prep_pass0, d_pa, sizeof(PrepAgg), hipMemcpyDeviceToHost, s));
       SHD_HIP(hipEventRecord(ev_pt, s));
       SHD_HIP(hipEventSynchronize(ev_pg));
     } else if (fast1)
@@ -1919,11 +1917,10 @@ struct PatternEngine : Engine {
       SHD_CHECK_LAUNCH();
       hipLaunchKernelGGL(k_finish_prep, dim3(1), dim3(kBlock), 0, s, (const PrepAgg*)d_blk.as<PrepAgg>(), nblk, d_pa);
       SHD_CHECK_LAUNCH();
-      SHD_HIP(hipMemcpyAsync(h_agg.p, d_agg.p, 64, hipMemcpyDeviceToHost, s));
+      agg.fetch(&PatternTotals::prep, s);
       SHD_HIP(hipStreamSynchronize(s));
     }
-    PrepAgg pg;
-    std::memcpy(&pg, h_agg.p, sizeof(pg));
+    PrepAgg pg = h_agg.prep;
     mark("prepare");
     // an unpartitioned plan retired partials that the last event of an earlier
     // push expired (global expiry: they are gone in the reference too); a push
@@ -2015,7 +2012,7 @@ struct PatternEngine : Engine {
     }
     if (fused) {   // the complete PrepAgg (k_ks_tfold after the first pass)
       SHD_HIP(hipEventSynchronize(ev_pt));
-      std::memcpy(&pg, h_agg.as<char>() + 256, sizeof(pg));
+      pg = h_agg.prep_pass0;
     }
     if (pg.ovf || knob_on(Knob::TS64)) {   // SHD_TS64: force the 64-bit path (tests)
       // some timestamp is more than 2^31 ms away from the batch's first event
@@ -2186,7 +2183,7 @@ struct PatternEngine : Engine {
       } else if (rlist) {
         // sparse keys: the deferred positions compacted into a list (per-tile
         // counts from k_forward_scan), then one lane per deferred walk
-        uint32_t* d_ndef = reinterpret_cast<uint32_t*>(d_agg.as<char>() + 240);
+        uint32_t* d_ndef = &agg.dev()->n_deferred;
         scan_exclusive_u32(d_bcnt.as<uint32_t>() + 2 * ntile, d_boff.as<uint32_t>() + 2 * ntile, ntile, d_ndef, d_scan,
                            s);
         d_dlist.reserve((size_t)n_ext * 4);
@@ -2222,18 +2219,17 @@ struct PatternEngine : Engine {
     mark("forward_scan");
 
     // ---- per-tile compaction offsets for matches and open partials (position order)
-    uint32_t* d_mo = reinterpret_cast<uint32_t*>(d_agg.as<char>() + 128);
-    scan_exclusive_u32(d_bcnt.as<uint32_t>(), d_boff.as<uint32_t>(), ntile, d_mo, d_scan, s);
-    scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, d_mo + 1, d_scan, s);
+    scan_exclusive_u32(d_bcnt.as<uint32_t>(), d_boff.as<uint32_t>(), ntile, &agg.dev()->n_match, d_scan, s);
+    scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, &agg.dev()->n_open, d_scan,
+                       s);
     mark("compact");
-    SHD_HIP(hipMemcpyAsync(h_agg.as<char>() + 64, d_agg.as<char>() + 64, 80, hipMemcpyDeviceToHost, s));
+    agg.fetch(&PatternTotals::scan, &PatternTotals::tail_, s);
     // time of the push's last event in arrival order (NeedNfa hand-over: global expiry of unpartitioned plans)
-    SHD_HIP(hipMemcpyAsync(h_agg.as<char>() + 192, b.cs.ts + (n - 1), 8, hipMemcpyDeviceToHost, s));
+    SHD_HIP(hipMemcpyAsync(&h_agg.t_last, b.cs.ts + (n - 1), 8, hipMemcpyDeviceToHost, s));
     SHD_HIP(hipStreamSynchronize(s));
-    ScanOut so;
-    std::memcpy(&so, h_agg.as<char>() + 64, sizeof(so));
-    const uint32_t m = h_agg.as<uint32_t>()[32];
-    const uint32_t n_open = h_agg.as<uint32_t>()[33];
+    const ScanOut so = h_agg.scan;
+    const uint32_t m = h_agg.n_match;
+    const uint32_t n_open = h_agg.n_open;
     if (so.violation)   // the generic NFA engine takes over (shd_push replays the open partials)
       throw NeedNfa("pattern engine: event timestamps decrease within a key under `within`");
     if (so.pruned) {
@@ -2386,7 +2382,7 @@ struct PatternEngine : Engine {
     if (b.stream == sB) last_b_seq = seq + n - 1;
     seq += n;
     if (b.advance_time && t_end > now) now = t_end;
-    std::memcpy(&t_last, h_agg.as<char>() + 192, 8);
+    t_last = agg.host().t_last;
     counters.events += n;
     counters.matches += m;
     counters.partial_scans += (int64_t)so.steps;

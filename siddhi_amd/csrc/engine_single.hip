@@ -2596,6 +2596,33 @@ int plain_load_attr(const Plan& p, int e) {
 
 }  // namespace
 
+// The single-stream engine's per-push readback block (SingleEngine::tot).
+// Fields sit in 8-byte slots; spans read back together are contiguous.
+struct SingleTotals {
+  uint32_t n_pass;      // scan_exclusive_u32 over k_filter's counts, or k_filter_items: events passing the filters
+  uint32_t n_runs;      // scan_exclusive_u32: key runs of a partitioned filter query
+  uint64_t n_expired;   // memset, k_count_expired: items the push expires (time windows)
+  uint64_t kmax;        // reduce_max_u64, or memset + k_filter_items: largest group id
+  uint32_t n_heads, n_heads_pad_;   // scan_exclusive_u32: groups of the sorted operation stream (exact fold)
+  uint32_t n_first, n_first_pad_;   // scan_exclusive_u32: output rows of emit_rows
+  // operand statistics of the segmented scans' range guard: one 3-word array
+  // to k_make_items / k_filter_items / k_operand_stats; flags and emax are
+  // zeroed by one memset, emin and its pad filled with 0xFF by another
+  uint32_t op_flags, op_emax;
+  uint32_t op_emin, op_emin_pad_;
+  uint32_t wc_overflow, wc_overflow_pad_;   // memset, k_wc_check: a chunk beyond the LDS capacity
+  uint32_t cw_call, cw_region;   // memset (both), k_cw_regions (a 2-word array): largest call / region of the call-window path
+  uint64_t cw_rows;     // rows of the call-window path: scan_exclusive_u32 (low word) + memset (high), or the rows kernels
+};
+static_assert(offsetof(SingleTotals, n_pass) == 0 && offsetof(SingleTotals, n_runs) == 4 &&
+                  offsetof(SingleTotals, n_expired) == 8 && offsetof(SingleTotals, kmax) == 16 &&
+                  offsetof(SingleTotals, n_heads) == 24 && offsetof(SingleTotals, n_first) == 32 &&
+                  offsetof(SingleTotals, op_flags) == 40 && offsetof(SingleTotals, op_emax) == 44 &&
+                  offsetof(SingleTotals, op_emin) == 48 && offsetof(SingleTotals, wc_overflow) == 56 &&
+                  offsetof(SingleTotals, cw_call) == 64 && offsetof(SingleTotals, cw_region) == 68 &&
+                  offsetof(SingleTotals, cw_rows) == 72 && sizeof(SingleTotals) <= 128,
+              "SingleTotals device layout");
+
 struct SingleEngine : Engine {
   bool agg_mode = false;
   std::vector<int> filters;
@@ -2614,9 +2641,9 @@ struct SingleEngine : Engine {
   std::vector<int> types;
   int nagg = 0;
   // per-batch scratch
-  DevBuf d_offs, d_call_of, d_last_ts, d_now, d_flags, d_cnt, d_off, d_pkey, d_start, d_run, d_tot, d_scan, d_sort,
+  DevBuf d_offs, d_call_of, d_last_ts, d_now, d_flags, d_cnt, d_off, d_pkey, d_start, d_run, d_scan, d_sort,
       d_pmax;
-  PinnedBuf h_tot;
+  ReadbackBlock<SingleTotals> tot;
   // window items: carry [0, C) + new; double-buffered
   int64_t C = 0;
   int cur = 0;
@@ -2899,8 +2926,7 @@ struct SingleEngine : Engine {
     d_flags.reserve(n);
     d_cnt.reserve(n * 4);
     d_off.reserve(n * 4);
-    d_tot.reserve(128);
-    h_tot.reserve(128);
+    tot.reserve();
     if (partitioned) d_pkey.reserve(n * 8);
     FilterArgs fa{};
     fa.cs = b.cs;
@@ -2922,8 +2948,7 @@ struct SingleEngine : Engine {
       hipLaunchKernelGGL(k_filter, dim3(grid_cover(n)), dim3(kBlock), 0, s, d_fa, n, d_flags.as<uint8_t>(),
                          d_cnt.as<uint32_t>(), d_pkey.as<uint64_t>());
       SHD_CHECK_LAUNCH();
-      uint32_t* d_m = (uint32_t*)d_tot.p;
-      scan_exclusive_u32(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n, d_m, d_scan, s);
+      scan_exclusive_u32(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n, &tot.dev()->n_pass, d_scan, s);
       mark("filter");
       if (!agg_mode) push_filter(b, ncalls, n);
       else push_agg(b, ncalls, n);
@@ -2985,8 +3010,6 @@ struct SingleEngine : Engine {
 
   void push_filter(const Staged& b, int64_t ncalls, int64_t n) {
     hipStream_t s = stream;
-    uint32_t* d_m = (uint32_t*)d_tot.p;
-    uint32_t* d_r = d_m + 1;
     if (partitioned) {
       d_start.reserve(n * 4);
       d_run.reserve(n * 4);
@@ -2995,12 +3018,12 @@ struct SingleEngine : Engine {
                          d_start.as<uint32_t>());
       SHD_CHECK_LAUNCH();
       // run id of event i = (#starts up to and including i) - 1
-      scan_exclusive_u32(d_start.as<uint32_t>(), d_run.as<uint32_t>(), n, d_r, d_scan, s);
+      scan_exclusive_u32(d_start.as<uint32_t>(), d_run.as<uint32_t>(), n, &tot.dev()->n_runs, d_scan, s);
     }
-    SHD_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 8, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::n_pass, &SingleTotals::n_runs, s);
     SHD_HIP(hipStreamSynchronize(s));
-    uint32_t m = h_tot.as<uint32_t>()[0];
-    uint32_t nruns = h_tot.as<uint32_t>()[1];
+    uint32_t m = tot.host().n_pass;
+    uint32_t nruns = tot.host().n_runs;
     if (m > 0) {
       out.ensure(m, s);
       ProjArgs pa{};
@@ -3080,11 +3103,8 @@ struct SingleEngine : Engine {
     hipLaunchKernelGGL(k_first_counts, dim3(grid_for(m)), dim3(kBlock), 0, s, (const uint8_t*)first.as<uint8_t>(), C,
                        total, fcnt.as<uint32_t>());
     SHD_CHECK_LAUNCH();
-    uint32_t* d_f = (uint32_t*)(d_tot.as<uint64_t>() + 4);
-    scan_exclusive_u32(fcnt.as<uint32_t>(), foff.as<uint32_t>(), m, d_f, d_scan, s);
-    SHD_HIP(hipMemcpyAsync(h_tot.as<uint64_t>() + 4, d_f, 4, hipMemcpyDeviceToHost, s));
-    SHD_HIP(hipStreamSynchronize(s));
-    const int64_t nrows = h_tot.as<uint32_t>()[8];
+    const int64_t nrows =
+        scan(fcnt.as<uint32_t>(), foff.as<uint32_t>(), m, &tot.dev()->n_first, &tot.host().n_first, d_scan);
     if (nrows <= 0) return;
     out.ensure(nrows, s);
     EmitArgs ea{};
@@ -3235,8 +3255,8 @@ struct SingleEngine : Engine {
     wa.dsum = g_dsum.as<double>();
     wa.gcnt = g_cnt.as<int64_t>();
     wa.nkeys = g_nkeys;
-    unsigned int* d_flag = (unsigned int*)(d_tot.as<uint64_t>() + 7);
-    SHD_HIP(hipMemsetAsync(d_flag, 0, 4, s));
+    unsigned int* d_flag = &tot.dev()->wc_overflow;
+    tot.clear(&SingleTotals::wc_overflow, 0, s);
     wa.flag = d_flag;
     const WcArgs* d_wa = dev_args(wa);
     hipLaunchKernelGGL(k_wc_bounds, dim3(grid_for(K + 1)), dim3(kBlock), 0, s, d_wa, kc, K, F, (int)ncalls,
@@ -3245,9 +3265,9 @@ struct SingleEngine : Engine {
     hipLaunchKernelGGL(k_wc_check, dim3(grid_for(K)), dim3(kBlock), 0, s, (const int64_t*)wc_cp.as<int64_t>(),
                        (const int64_t*)wc_ce.as<int64_t>(), K, d_flag);
     SHD_CHECK_LAUNCH();
-    SHD_HIP(hipMemcpyAsync(h_tot.as<uint64_t>() + 7, d_flag, 4, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::wc_overflow, s);
     SHD_HIP(hipStreamSynchronize(s));
-    if (h_tot.as<uint32_t>()[14]) return false;   // a chunk beyond the LDS capacity
+    if (tot.host().wc_overflow) return false;   // a chunk beyond the LDS capacity
     seg_items.reserve((size_t)total * sizeof(SegItem<NC>));
     hipLaunchKernelGGL(k_seg_pack<NC>, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(sa),
                        (const uint64_t*)iargv[cur].as<uint64_t>(), (const uint8_t*)iargn[cur].as<uint8_t>(),
@@ -3423,7 +3443,7 @@ struct SingleEngine : Engine {
     d_cw_status.reserve((size_t)ncalls * 8);
     SHD_HIP(hipMemsetAsync(d_cw_status.p, 0, (size_t)ncalls * 8, s));
     ca.status = d_cw_status.as<uint64_t>();
-    ca.nrows = d_tot.as<uint64_t>() + 9;
+    ca.nrows = &tot.dev()->cw_rows;
     const CwArgs* d_ca = dev_args(ca);
     if (kmax < (uint64_t)kCwDirectG && !knob_on(Knob::CW_HASH)) {
       // rows per call (distinct groups) -> each call's first row
@@ -3433,9 +3453,9 @@ struct SingleEngine : Engine {
         hipLaunchKernelGGL(k_cw_count<kCwDirectG>, dim3((unsigned)ncalls), dim3(kBlock), 0, s, d_ca, (int)ncalls,
                            d_cw_cnt.as<uint32_t>());
         SHD_CHECK_LAUNCH();
-        scan_exclusive_u32(d_cw_cnt.as<uint32_t>(), d_cw_base.as<uint32_t>(), ncalls,
-                           (uint32_t*)(d_tot.as<uint64_t>() + 9), d_scan, s);
-        SHD_HIP(hipMemsetAsync(d_tot.as<uint32_t>() + 19, 0, 4, s));   // (the row count's high word)
+        uint32_t* d_rows = reinterpret_cast<uint32_t*>(&tot.dev()->cw_rows);   // the scan writes the low word
+        scan_exclusive_u32(d_cw_cnt.as<uint32_t>(), d_cw_base.as<uint32_t>(), ncalls, d_rows, d_scan, s);
+        SHD_HIP(hipMemsetAsync(d_rows + 1, 0, 4, s));   // (the row count's high word)
       }
       if (defer) {
         defer->push_back(d_ca);
@@ -3455,7 +3475,7 @@ struct SingleEngine : Engine {
         default: callwin_launch<4>(d_ca, ncalls, call, region); break;
       }
     }
-    SHD_HIP(hipMemcpyAsync(h_tot.as<uint64_t>() + 9, d_tot.as<uint64_t>() + 9, 8, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::cw_rows, s);
     mark("call_window");
     // the group tables: the window state after the push.  Only groups of the
     // carried items (the state before the push) and of the final window can
@@ -3475,7 +3495,7 @@ struct SingleEngine : Engine {
     mark("group_tables");
     if (defer && !defer->empty() && defer->back() == d_ca) return;
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t nrows = m > 0 ? (int64_t)h_tot.as<uint64_t>()[9] : 0;
+    const int64_t nrows = m > 0 ? (int64_t)tot.host().cw_rows : 0;
     q.out.count += nrows;
     q.counters.matches += nrows;
   }
@@ -3621,11 +3641,11 @@ struct SingleEngine : Engine {
 
   void push_agg(const Staged& b, int64_t ncalls, int64_t n) {
     hipStream_t s = stream;
-    SHD_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 4, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::n_pass, s);
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t m = h_tot.as<uint32_t>()[0];
-    SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 5, 0, 8, s));
-    SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 6, 0xFF, 8, s));
+    const int64_t m = tot.host().n_pass;
+    tot.clear(&SingleTotals::op_flags, &SingleTotals::op_emax, 0, s);
+    tot.clear(&SingleTotals::op_emin, &SingleTotals::op_emin_pad_, 0xFF, s);
     // items: carry slot `cur` already holds [0, C); build the new item set in slot `cur`
     grow_items(C + m);
     const int64_t cap = icap[cur];
@@ -3635,7 +3655,7 @@ struct SingleEngine : Engine {
                        (const int32_t*)d_call_of.as<int32_t>(), (const int64_t*)d_now.as<int64_t>(),
                        ikey[cur].as<uint64_t>(), its[cur].as<int64_t>(), iargv[cur].as<uint64_t>(),
                        iargn[cur].as<uint8_t>(), ievrow.as<int32_t>(), icall.as<int32_t>(), inow.as<int64_t>(), cap,
-                       (uint32_t*)(d_tot.as<uint64_t>() + 5));
+                       &tot.dev()->op_flags);
     SHD_CHECK_LAUNCH();
     if (ngk && !gdense) gdict_assign(m, std::max<int64_t>(m, 1));
     mark("window_items");
@@ -3669,23 +3689,23 @@ struct SingleEngine : Engine {
     d_cw_citem.reserve((size_t)(ncalls + 1) * 4);
     fu.citem = d_cw_citem.as<uint32_t>();
     fu.ncalls = (int)ncalls;
-    fu.m_out = (uint32_t*)d_tot.p;
-    SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 2, 0, 8, s));
-    fu.kmax_out = (unsigned long long*)(d_tot.as<uint64_t>() + 2);
-    SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 5, 0, 8, s));
-    SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 6, 0xFF, 8, s));
+    fu.m_out = &tot.dev()->n_pass;
+    tot.clear(&SingleTotals::kmax, 0, s);
+    fu.kmax_out = (unsigned long long*)&tot.dev()->kmax;
+    tot.clear(&SingleTotals::op_flags, &SingleTotals::op_emax, 0, s);
+    tot.clear(&SingleTotals::op_emin, &SingleTotals::op_emin_pad_, 0xFF, s);
     fu.nch = seg_mode ? nch : 0;
     for (int c = 0; c < nch; c++) {
       fu.ch_agg[c] = ch_agg[c];
       fu.ch_t[c] = ch_type[c];
     }
-    fu.opstats = (uint32_t*)(d_tot.as<uint64_t>() + 5);
+    fu.opstats = &tot.dev()->op_flags;
     hipLaunchKernelGGL(k_filter_items, dim3((unsigned)ntiles), dim3(kBlock), 0, s, dev_args(fu), n);
     SHD_CHECK_LAUNCH();
-    SHD_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 24, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::n_pass, &SingleTotals::kmax, s);
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t m = h_tot.as<uint32_t>()[0];
-    fused_kmax = h_tot.as<uint64_t>()[2];
+    const int64_t m = tot.host().n_pass;
+    fused_kmax = tot.host().kmax;
     if (ngk && !gdense) gdict_assign(m, std::max<int64_t>(n, 1));
     mark("filter_items");
     push_agg_tail(b, ncalls, n, m, true);
@@ -3728,11 +3748,11 @@ struct SingleEngine : Engine {
       }
       e_ready = true;
     };
-    unsigned long long* d_x = (unsigned long long*)(d_tot.as<uint64_t>() + 1);
-    uint64_t* d_kmax = d_tot.as<uint64_t>() + 2;
+    unsigned long long* d_x = (unsigned long long*)&tot.dev()->n_expired;
+    uint64_t* d_kmax = &tot.dev()->kmax;
     if (!len_win) {
       make_expiry();
-      SHD_HIP(hipMemsetAsync(d_x, 0, 8, s));
+      tot.clear(&SingleTotals::n_expired, 0, s);
       hipLaunchKernelGGL(k_count_expired, dim3(grid_for(total, 4, 2048)), dim3(kBlock), 0, s,
                          (const uint32_t*)e_exp.as<uint32_t>(), total, d_x);
       SHD_CHECK_LAUNCH();
@@ -3755,14 +3775,14 @@ struct SingleEngine : Engine {
       hipLaunchKernelGGL(k_operand_stats, dim3((unsigned)std::min<int64_t>(1024, ceil_div(m, kBlock))), dim3(kBlock), 0,
                          s, (const uint64_t*)iargv[cur].as<uint64_t>(), (const uint8_t*)iargn[cur].as<uint8_t>(), cap,
                          C, m, nch, (const int*)d_chmeta.as<int>(), (const int*)d_chmeta.as<int>() + kMaxChan,
-                         (uint32_t*)(d_tot.as<uint64_t>() + 5));
+                         &tot.dev()->op_flags);
       SHD_CHECK_LAUNCH();
     }
     const bool cw_cand = callwin_candidate(ncalls, total);
     if (cw_cand) {
       d_cw_citem.reserve((size_t)(ncalls + 1) * 4);
       d_cw_clb.reserve((size_t)std::max<int64_t>(ncalls, 1) * 4);
-      SHD_HIP(hipMemsetAsync(d_tot.as<uint64_t>() + 8, 0, 8, s));
+      tot.clear(&SingleTotals::cw_call, &SingleTotals::cw_region, 0, s);
       if (!fused) {   // (k_filter_items wrote them)
         hipLaunchKernelGGL(k_cw_citem, dim3(grid_for(ncalls + 1)), dim3(kBlock), 0, s,
                            (const int64_t*)d_offs.as<int64_t>(), (const uint32_t*)d_off.as<uint32_t>(), n, m, C,
@@ -3772,18 +3792,19 @@ struct SingleEngine : Engine {
       hipLaunchKernelGGL(k_cw_regions, dim3(grid_for(ncalls)), dim3(kBlock), 0, s,
                          (const uint32_t*)e_exp.as<uint32_t>(), len_win ? wparam : (int64_t)0,
                          (const uint32_t*)d_cw_citem.as<uint32_t>(), (int)ncalls, d_cw_clb.as<uint32_t>(),
-                         (uint32_t*)(d_tot.as<uint64_t>() + 8));
+                         &tot.dev()->cw_call);
       SHD_CHECK_LAUNCH();
     }
-    SHD_HIP(hipMemcpyAsync(h_tot.p, d_tot.p, 72, hipMemcpyDeviceToHost, s));
+    tot.fetch(&SingleTotals::n_pass, &SingleTotals::cw_region, s);
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t X = len_win ? std::max<int64_t>(0, total - wparam) : (int64_t)h_tot.as<uint64_t>()[1];
-    uint64_t kmax = h_tot.as<uint64_t>()[2];
+    const SingleTotals& ht = tot.host();
+    const int64_t X = len_win ? std::max<int64_t>(0, total - wparam) : (int64_t)ht.n_expired;
+    uint64_t kmax = ht.kmax;
     if (kmax_fused) kmax = std::max(kmax_seen, fused_kmax);
     kmax_seen = std::max(kmax_seen, kmax);
     kmax_known = true;
-    const uint32_t cw_call = cw_cand ? h_tot.as<uint32_t>()[16] : 0u;
-    const uint32_t cw_region = cw_cand ? h_tot.as<uint32_t>()[17] : 0u;
+    const uint32_t cw_call = cw_cand ? ht.cw_call : 0u;
+    const uint32_t cw_region = cw_cand ? ht.cw_region : 0u;
     if (guard) {
       // Segmented scans reassociate the reference's running `sum += v; sum -= v`
       // (SumAttributeAggregatorExecutor.java:184-198).  With a non-finite
@@ -3794,13 +3815,12 @@ struct SingleEngine : Engine {
       // bit-exact sequential fold (the group tables carry over).
       // the span and the signs are over every operand since reset (window
       // items of earlier pushes included), not just this push's
-      const uint32_t* fl = h_tot.as<uint32_t>() + 10;
-      op_emax = std::max(op_emax, fl[1]);
-      op_emin = std::min(op_emin, fl[2]);
-      op_signs |= fl[0] & (kOpNeg | kOpPos);
+      op_emax = std::max(op_emax, ht.op_emax);
+      op_emin = std::min(op_emin, ht.op_emin);
+      op_signs |= ht.op_flags & (kOpNeg | kOpPos);
       const bool wide = op_emin != 0xFFFFFFFFu && op_emax > op_emin + kSegMaxExpSpan;
       const bool mixed = (op_signs & (kOpNeg | kOpPos)) == (kOpNeg | kOpPos);
-      if ((fl[0] & 1u) || wide || mixed) {
+      if ((ht.op_flags & 1u) || wide || mixed) {
         seg_mode = false;
         seg_unsafe = true;
       }
@@ -3839,7 +3859,7 @@ struct SingleEngine : Engine {
       if (multi && !margs.empty()) {
         callwin_direct_multi(margs, mnch, ncalls, cw_call, cw_region);
         SHD_HIP(hipStreamSynchronize(stream));
-        const int64_t nrows = m > 0 ? (int64_t)h_tot.as<uint64_t>()[9] : 0;
+        const int64_t nrows = m > 0 ? (int64_t)tot.host().cw_rows : 0;
         for (auto* qp : wmembers) {
           qp->out.count += nrows;
           qp->counters.matches += nrows;
@@ -3893,11 +3913,8 @@ struct SingleEngine : Engine {
       hoff.reserve(nops * 4);
       hipLaunchKernelGGL(k_seg_heads, dim3(grid_for(nops)), dim3(kBlock), 0, s, sk, nops, heads.as<uint32_t>());
       SHD_CHECK_LAUNCH();
-      uint32_t* d_h = (uint32_t*)(d_tot.as<uint64_t>() + 3);
-      scan_exclusive_u32(heads.as<uint32_t>(), hoff.as<uint32_t>(), nops, d_h, d_scan, s);
-      SHD_HIP(hipMemcpyAsync(h_tot.as<uint64_t>() + 3, d_h, 4, hipMemcpyDeviceToHost, s));
-      SHD_HIP(hipStreamSynchronize(s));
-      const int64_t nheads = h_tot.as<uint32_t>()[6];
+      const int64_t nheads =
+          scan(heads.as<uint32_t>(), hoff.as<uint32_t>(), nops, &tot.dev()->n_heads, &tot.host().n_heads, d_scan);
       hlist.reserve(std::max<int64_t>(nheads, 1) * 4);
       hipLaunchKernelGGL(k_head_list, dim3(grid_for(nops)), dim3(kBlock), 0, s, (const uint32_t*)heads.as<uint32_t>(),
                          (const uint32_t*)hoff.as<uint32_t>(), nops, hlist.as<uint32_t>());

@@ -1199,6 +1199,20 @@ int bits_for(uint64_t v) {
 }  // namespace
 
 // ====================================================================== host
+// The keyed window engine's readback block (WindowXEngine::tot): every value
+// is read back on its own, right after the call that writes it.
+struct WindowTotals {
+  uint32_t scan_total;   // scan_exclusive_u32 (WindowXEngine::scan)
+  uint64_t kmax;         // reduce_max_u64: largest partition key of the items
+};
+static_assert(offsetof(WindowTotals, scan_total) == 0 && offsetof(WindowTotals, kmax) == 8 &&
+                  sizeof(WindowTotals) <= 64,
+              "WindowTotals device layout");
+struct WindowTotalsHost : WindowTotals {
+  uint32_t n_timer;   // copy of the time lane's timer count (ntimer)
+  int64_t last_out;   // copy of the last output sequence (last_out)
+};
+
 struct WindowXEngine : Engine {
   std::vector<int> filters;
   int wkind = 0;
@@ -1236,12 +1250,13 @@ struct WindowXEngine : Engine {
   int64_t tb_epoch = -1;   // stream.current.event timeBatch: global chunk id of the last flush
   // per-push scratch
   DevBuf d_offs, d_call_of, d_last, d_call_now, d_F, d_fnow, d_flags, d_cnt, d_off, d_pkey, d_start,
-      d_run, d_runs_before, d_tot, d_scan, d_sort, kw, kn, kh, spk, spk2, sp, sp2, head, hscan, segS, segid, segCk,
+      d_run, d_runs_before, d_scan, d_sort, kw, kn, kh, spk, spk2, sp, sp2, head, hscan, segS, segid, segCk,
       pA, pB, proom, proom_off, eopp, etid, rec, tF, tHead, tSeg, ntimer, pout_pk, pout_v, pcnt, pcnt_off, last_out,
       seg_pk, okeep, okoff, tperm, tperm2, tk32, tk32b, tk64, tk64b, trank, sF, nops_b, opscan, op_item, op_add, op_on,
       op_chunk, op_now, op_seq, osid, osid2, oq, oq2, ohead, ohoff, ohl, resv, resn, rowflag, rowsrc, roff, rkey, rkey2,
       rq, rq2, keep, koff, pend_tmp_pk, pend_tmp_v, pend_idx, pend_idx2, pend_key2;
-  PinnedBuf h_tot, h_last, h_pin;
+  PinnedBuf h_last, h_pin;
+  ReadbackBlock<WindowTotals, WindowTotalsHost> tot;
   std::vector<int64_t> h_offs, h_now;
   std::vector<int32_t> h_F;
   std::vector<int64_t> h_fnow;
@@ -1370,18 +1385,10 @@ struct WindowXEngine : Engine {
     SHD_HIP(hipMemcpyAsync(d.p, h_pin.p, v.size() * sizeof(T), hipMemcpyHostToDevice, stream));
     SHD_HIP(hipStreamSynchronize(stream));
   }
-  uint32_t read_u32(const void* dev) {
-    h_tot.reserve(64);
-    SHD_HIP(hipMemcpyAsync(h_tot.p, dev, 4, hipMemcpyDeviceToHost, stream));
-    SHD_HIP(hipStreamSynchronize(stream));
-    return h_tot.as<uint32_t>()[0];
-  }
-  // exclusive scan; returns the total
+  // exclusive scan; returns the total (every scan of this engine is read back on its own)
   uint32_t scan(const uint32_t* in, uint32_t* outp, int64_t n) {
-    if (n <= 0) return 0;
-    d_tot.reserve(64);
-    scan_exclusive_u32(in, outp, n, d_tot.as<uint32_t>(), d_scan, stream);
-    return read_u32(d_tot.p);
+    tot.reserve();
+    return Engine::scan(in, outp, n, &tot.dev()->scan_total, &tot.host().scan_total, d_scan);
   }
 
   // ---- push
@@ -1553,12 +1560,11 @@ struct WindowXEngine : Engine {
       const uint32_t* spv = sp.as<uint32_t>();
       const uint64_t* spkv = spk.as<uint64_t>();
       if (partitioned) {
-        d_tot.reserve(64);
-        reduce_max_u64(ipk[cur].as<uint64_t>(), total, d_tot.as<uint64_t>() + 1, s);
-        h_tot.reserve(64);
-        SHD_HIP(hipMemcpyAsync(h_tot.p, d_tot.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost, s));
+        tot.reserve();
+        reduce_max_u64(ipk[cur].as<uint64_t>(), total, &tot.dev()->kmax, s);
+        tot.fetch(&WindowTotals::kmax, s);
         SHD_HIP(hipStreamSynchronize(s));
-        const uint64_t kmax = h_tot.as<uint64_t>()[0];
+        const uint64_t kmax = tot.host().kmax;
         spk2.reserve(total * 8);
         sp2.reserve(total * 4);
         bool alt = false;
@@ -1660,7 +1666,8 @@ struct WindowXEngine : Engine {
       la.last_out = last_out.as<int64_t>();
       hipLaunchKernelGGL(k_xw_time_lane, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, dev_args(la));
       SHD_CHECK_LAUNCH();
-      nt = read_u32(ntimer.p);
+      tot.reserve();
+      nt = read_u32(ntimer.p, &tot.host().n_timer);
       lane_ran = true;
     } else if (total > 0) {   // no window: items never expire
       hipLaunchKernelGGL(k_xw_fill_u64, dim3(grid_cover(total)), dim3(kBlock), 0, s, eopp.as<uint64_t>(), total, kNoOpp);
@@ -1937,10 +1944,10 @@ struct WindowXEngine : Engine {
     // time windows: notify entries still queued, the window's last time
     if (time_like() && timers) update_pending(nseg, nf, lane_ran);
     if (time_like() && !partitioned && lane_ran && nseg > 0) {
-      h_tot.reserve(64);
-      SHD_HIP(hipMemcpyAsync(h_tot.p, last_out.p, 8, hipMemcpyDeviceToHost, s));
+      tot.reserve();
+      SHD_HIP(hipMemcpyAsync(&tot.host().last_out, last_out.p, 8, hipMemcpyDeviceToHost, s));
       SHD_HIP(hipStreamSynchronize(s));
-      last_global = h_tot.as<int64_t>()[0];
+      last_global = tot.host().last_out;
     }
     cur = oth;
     C = kept;

@@ -191,14 +191,21 @@ __global__ __launch_bounds__(kBlock) void k_gdict_rehash(GDict o, GDict d) {
   }
 }
 
+// Totals of one GroupDict::assign (both written by scan_exclusive_u32).
+struct GDictTotals {
+  uint32_t n_miss;   // keys the lookup did not find
+  uint32_t n_new;    // distinct keys among them
+};
+static_assert(offsetof(GDictTotals, n_miss) == 0 && offsetof(GDictTotals, n_new) == 4, "GDictTotals device layout");
+
 // Host side of one dictionary (owned by an engine, used on its stream).
 struct GroupDict {
   int nk = 1;                 // key words per entry (>= 1)
   DevBuf tag, id, kw, kn;
   uint64_t cap = 0;
   int64_t count = 0;          // ids handed out so far
-  DevBuf miss, moff, midx, mh, midx_alt, mh_alt, lead, lrank, ctr, scan, sort;
-  PinnedBuf hctr;
+  DevBuf miss, moff, midx, mh, midx_alt, mh_alt, lead, lrank, scan, sort;
+  ReadbackBlock<GDictTotals> ctr;
 
   GDict view() const {
     return GDict{tag.as<unsigned long long>(), id.as<uint32_t>(), kw.as<uint64_t>(), kn.as<uint8_t>(), cap, nk};
@@ -241,15 +248,14 @@ struct GroupDict {
     reserve(1, s);
     miss.reserve(m * 4);
     moff.reserve(m * 4);
-    ctr.reserve(64);
-    hctr.reserve(64);
+    ctr.reserve();
     hipLaunchKernelGGL(k_gdict_lookup, dim3(grid_cover(m)), dim3(kBlock), 0, s, view(), m, gh, gkw, gkn, gstride, off,
                        out, miss.as<uint32_t>());
     SHD_CHECK_LAUNCH();
-    scan_exclusive_u32(miss.as<uint32_t>(), moff.as<uint32_t>(), m, ctr.as<uint32_t>(), scan, s);
-    SHD_HIP(hipMemcpyAsync(hctr.p, ctr.p, 4, hipMemcpyDeviceToHost, s));
+    scan_exclusive_u32(miss.as<uint32_t>(), moff.as<uint32_t>(), m, &ctr.dev()->n_miss, scan, s);
+    ctr.fetch(&GDictTotals::n_miss, s);
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t nm = hctr.as<uint32_t>()[0];
+    const int64_t nm = ctr.host().n_miss;
     if (nm == 0) return;
     midx.reserve(nm * 4);
     mh.reserve(nm * 8);
@@ -268,10 +274,10 @@ struct GroupDict {
     hipLaunchKernelGGL(k_gdict_leaders, dim3(grid_cover(nm)), dim3(kBlock), 0, s, nm, sh, sidx, gkw, gkn, gstride, nk,
                        lead.as<uint32_t>());
     SHD_CHECK_LAUNCH();
-    scan_exclusive_u32(lead.as<uint32_t>(), lrank.as<uint32_t>(), nm, ctr.as<uint32_t>() + 1, scan, s);
-    SHD_HIP(hipMemcpyAsync(hctr.as<uint32_t>() + 1, ctr.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s));
+    scan_exclusive_u32(lead.as<uint32_t>(), lrank.as<uint32_t>(), nm, &ctr.dev()->n_new, scan, s);
+    ctr.fetch(&GDictTotals::n_new, s);
     SHD_HIP(hipStreamSynchronize(s));
-    const int64_t nu = hctr.as<uint32_t>()[1];
+    const int64_t nu = ctr.host().n_new;
     if (count + nu >= (int64_t)0xFFFFFFF0ll) throw Error(SHD_E_CAPACITY, "more than 2^32 distinct keys");
     reserve(count + nu, s);
     hipLaunchKernelGGL(k_gdict_insert, dim3(grid_cover(nm)), dim3(kBlock), 0, s, view(), nm, sh, sidx,

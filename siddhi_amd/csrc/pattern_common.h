@@ -365,6 +365,34 @@ struct KsInfo {
   uint32_t kb;
   int32_t bits;
 };
+
+// The pattern engine's per-push readback block (PatternEngine::agg).  The
+// device layout is fixed: prepare and scan each own a 64-byte slot, and the
+// two compaction totals follow so that one copy from `scan` to `tail_`
+// delivers everything the push reads after the forward scan.
+struct PatternTotals {
+  PrepAgg prep;         // k_finish_prep, or keyed_sort_front + keyed_sort_pass0 (fused sort); host upload of the identity
+  ScanOut scan;         // k_finish_scan; zeroed by the same upload as `prep`
+  char scan_pad_[64 - sizeof(ScanOut)];   // rest of the scan slot (uploaded with it)
+  uint32_t n_match;     // scan_exclusive_u32: completed matches
+  uint32_t n_open;      // scan_exclusive_u32: partials still open
+  uint32_t tail_[2];    // unwritten; the last 8 bytes of the totals' readback
+  char pad_[232 - 144];
+  KsInfo ks;            // keyed_sort_front (fused sort)
+  uint32_t n_deferred;  // scan_exclusive_u32: deferred walks of the resume list
+};
+static_assert(offsetof(PatternTotals, prep) == 0 && offsetof(PatternTotals, scan) == 64 &&
+                  offsetof(PatternTotals, n_match) == 128 && offsetof(PatternTotals, n_open) == 132 &&
+                  offsetof(PatternTotals, tail_) + sizeof(uint32_t[2]) == 64 + 80 &&
+                  offsetof(PatternTotals, ks) == 232 && offsetof(PatternTotals, n_deferred) == 240 &&
+                  sizeof(PatternTotals) <= 256,
+              "PatternTotals device layout");
+// Host image: the device fields, then what only the host reads.
+struct PatternTotalsHost : PatternTotals {
+  int64_t t_last;        // time of the push's last event in arrival order (copied from the batch's ts column)
+  PrepAgg prep_pass0;    // fused sort: `prep` again once keyed_sort_pass0 completed it
+};
+
 // The one attribute f1's loads read (-1: none or the pushed stream is not A;
 // -2: f1 is not a pre-decoded chain over one attribute -- not fusable).
 int keyed_sort_f1_attr(const DFilters& f1, bool is_a);
