@@ -9,6 +9,7 @@
 #include <stdexcept>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/siddhi_hip.h"
@@ -84,6 +85,10 @@ struct DevBuf {
     b = (b + 255) & ~size_t(255);
     SHD_HIP(hipMalloc(&p, b));
     cap = b;
+  }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };

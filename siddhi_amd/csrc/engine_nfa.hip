@@ -3044,12 +3044,11 @@ void layout_offsets(NfaLayout& Y) {
   Y.sew = (Y.SC + 1 + 63) / 64;
   Y.evw = (Y.EC + 1 + 63) / 64;
   Y.recw = (Y.RC + 1 + 63) / 64;
-  // 64 key states interleaved per block; SHD_NFA_INTERLEAVE=0 keeps one key
-  // state contiguous (measured slower on window lanes too: S4-seq 158 vs 182 M
-  // events/s, S4P-seqplus 190 vs 199 M)
+  // 64 key states interleaved per block (one contiguous state per key measured
+  // slower, on window lanes too: S4-seq 158 vs 182 M events/s, S4P-seqplus 190
+  // vs 199 M)
   Y.W = kLaneBlock;
-  if (knob_force(Knob::NFA_INTERLEAVE) == 0) Y.W = 1;
-  const int64_t falign = Y.W == 1 ? 16 : 256;
+  const int64_t falign = 256;
   int64_t off = 0;
   Y.nf = 0;
   auto field = [&](int64_t count, int sz) {

@@ -2081,7 +2081,7 @@ struct PatternEngine : Engine {
     if (grouped && (rmode != 0 || lockstep) && isB && bpos_mask && !knob_on(Knob::NO_BPOS) &&
         (e_key >= 8.0 || knob_on(Knob::BPOS))) {
       // e1 operands position-major too (same stream schema, columns the carry keeps)
-      uint32_t apos = knob_on(Knob::NO_APOS) ? 0u : (apos_mask & carry_mask);
+      uint32_t apos = apos_mask & carry_mask;
       for (int c = 0; c < kMaxCols; c++)
         if (((apos >> c) & 1u) && (c >= b.cs.ncols || c >= (int)typesA.size() || typesA[c] != b.cs.type[c]))
           apos &= ~(1u << c);
@@ -2345,9 +2345,9 @@ struct PatternEngine : Engine {
         skey32 = d_k32.as<uint32_t>();
         skey64 = d_k64.as<uint64_t>();
       }
-      if (logical != 2 && !knob_on(Knob::CARRY_SERIAL)) {
+      if (logical != 2) {
         ga.amask = carry_mask;
-        if (grouped && !knob_on(Knob::GATHER_ROWS)) {
+        if (grouped) {
           ga.sts32 = fin_sts32;
           ga.sts64 = fin_sts64;
           // the partition key attribute of stream A, a 32-bit plain column (sorted key == its value)

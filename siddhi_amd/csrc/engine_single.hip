@@ -37,7 +37,7 @@ constexpr uint32_t kInf = 0xFFFFFFFFu;
 constexpr uint32_t kAddBit = 0x80000000u;
 constexpr int64_t kMaxDenseKey = (int64_t)1 << 26;
 // segmented scans only while every operand seen so far is finite and the
-// non-zero magnitudes span at most 2^kSegMaxExpSpan (k_operand_stats)
+// non-zero magnitudes span at most 2^kSegMaxExpSpan (k_filter_items)
 constexpr uint32_t kSegMaxExpSpan = 30;
 // ... and all of one sign: a window of mixed signs can cancel to far below its
 // operands, where the reference's running sum keeps its rounding history
@@ -301,19 +301,6 @@ __device__ __forceinline__ void make_item(const ItemArgs& a, int64_t i, int64_t 
   if (a.time_window) inow[t] = call_now[c];
 }
 
-// New window items (one per filtered event), appended after the carried ones.
-__global__ __launch_bounds__(kBlock) void k_make_items(const ItemArgs* __restrict__ ap, int64_t n, const uint32_t* cnt, const uint32_t* off,
-                                                       const int32_t* call_of, const int64_t* call_now,
-                                                       uint64_t* ikey, int64_t* its, uint64_t* iargv, uint8_t* iargn,
-                                                       int32_t* ievrow, int32_t* icall, int64_t* inow, int64_t cap,
-                                                       uint32_t* null_key_flag) {
-  const ItemArgs& a = *ap;   // args live in device memory (Engine::dev_args)
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) {
-    if (!cnt[i]) continue;
-    make_item(a, i, off[i], call_of, call_now, ikey, its, iargv, iargn, ievrow, icall, inow, cap);
-  }
-}
-
 // Look-back status words: a device-coherent plain load (no read-modify-write:
 // many workgroups poll the same words, and atomics on one line serialise in L2)
 __device__ __forceinline__ uint64_t cw_status_load(const uint64_t* p) {
@@ -325,7 +312,7 @@ __device__ __forceinline__ uint64_t cw_status_load(const uint64_t* p) {
 // items at the tile's offset, found by a decoupled look-back over the tiles
 // (each tile publishes its count first).  Also: the first item of every
 // InputHandler call (citem, for the call-window path), the largest new group
-// id, and the range guard's operand statistics (k_operand_stats).
+// id, and the range guard's operand statistics (guard_operand).
 constexpr int kFiPer = 8;
 constexpr int kFiTile = kBlock * kFiPer;
 
@@ -463,49 +450,6 @@ __global__ __launch_bounds__(kBlock) void k_filter_items(const FusedArgs* __rest
 }
 
 // ---------------------------------------------------------------- group dictionary (gdict.h)
-
-// Range guard of the segmented-scan mode: over the new items' double / float
-// operands of the scanned channels, flags[0] |= 1 for a non-finite value,
-// flags[1] = max and flags[2] = min binary exponent of the non-zero values.
-// (One atomic per block; a grid of at most 1024 blocks.)
-__global__ __launch_bounds__(kBlock) void k_operand_stats(const uint64_t* argv, const uint8_t* argn, int64_t cap,
-                                                          int64_t C, int64_t m, int nch, const int* ch_agg,
-                                                          const int* ch_type, uint32_t* flags) {
-  uint32_t nf = 0, emax = 0, emin = 0xFFFFFFFFu;
-  for (int c = 0; c < nch; c++) {
-    const int g = ch_agg[c];
-    const int type = ch_type[c];
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < m; i += (int64_t)gridDim.x * kBlock) {
-      const int64_t t = C + i;
-      if (argn[(int64_t)g * cap + t]) continue;
-      guard_operand(argv[(int64_t)g * cap + t], type, nf, emax, emin);
-    }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    nf |= __shfl_xor(nf, o, 64);
-    const uint32_t a = __shfl_xor(emax, o, 64), b = __shfl_xor(emin, o, 64);
-    emax = a > emax ? a : emax;
-    emin = b < emin ? b : emin;
-  }
-  __shared__ uint32_t sh[3][kBlock / 64];
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][w] = nf;
-    sh[1][w] = emax;
-    sh[2][w] = emin;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int k = 1; k < kBlock / 64; k++) {
-      nf |= sh[0][k];
-      emax = sh[1][k] > emax ? sh[1][k] : emax;
-      emin = sh[2][k] < emin ? sh[2][k] : emin;
-    }
-    if (nf) atomicOr(&flags[0], nf);
-    atomicMax(&flags[1], emax);
-    atomicMin(&flags[2], emin);
-  }
-}
 
 // Expiry position of every window item.
 __global__ void k_expiry(int wkind, int64_t wparam, int64_t C, int64_t total, const int64_t* its,
@@ -1166,7 +1110,8 @@ struct SegArgs {
   int64_t nkeys;
 };
 
-// sorted-order copies of what the scan and the window search read
+// sorted-order copies of what the scan and the window search read (three and
+// four channels; one and two go through k_seg_pack + k_seg_gather_packed)
 template <int NC>
 __global__ __launch_bounds__(kBlock) void k_seg_gather(const SegArgs* __restrict__ ap, const uint32_t* sp,
                                                        const uint64_t* iargv, const uint8_t* iargn,
@@ -1634,15 +1579,6 @@ __device__ __forceinline__ double cw_operand(const CwArgs& a, int c, int64_t q, 
     case SHD_T_LONG: return (double)(int64_t)b;
     case SHD_T_FLOAT: return (double)v_f32(b);
     default: return v_f64(b);
-  }
-}
-
-// first item of every call (from the event -> item offsets of k_filter's scan)
-__global__ void k_cw_citem(const int64_t* __restrict__ offs, const uint32_t* __restrict__ off, int64_t n, int64_t m,
-                           int64_t C, int ncalls, uint32_t* __restrict__ citem) {
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c <= ncalls; c += gridDim.x * blockDim.x) {
-    const int64_t ev = offs[c];
-    citem[c] = (uint32_t)(C + (ev < n ? (int64_t)off[ev] : m));
   }
 }
 
@@ -2594,6 +2530,12 @@ int plain_load_attr(const Plan& p, int e) {
   return -1;
 }
 
+// an argument struct with a per-aggregator channel array (FoldArgs has none)
+template <class A, class = void>
+struct has_chan : std::false_type {};
+template <class A>
+struct has_chan<A, std::void_t<decltype(std::declval<A&>().chan)>> : std::true_type {};
+
 }  // namespace
 
 // The single-stream engine's per-push readback block (SingleEngine::tot).
@@ -2606,8 +2548,8 @@ struct SingleTotals {
   uint32_t n_heads, n_heads_pad_;   // scan_exclusive_u32: groups of the sorted operation stream (exact fold)
   uint32_t n_first, n_first_pad_;   // scan_exclusive_u32: output rows of emit_rows
   // operand statistics of the segmented scans' range guard: one 3-word array
-  // to k_make_items / k_filter_items / k_operand_stats; flags and emax are
-  // zeroed by one memset, emin and its pad filled with 0xFF by another
+  // to k_filter_items; flags and emax are zeroed by one memset, emin and its
+  // pad filled with 0xFF by another
   uint32_t op_flags, op_emax;
   uint32_t op_emin, op_emin_pad_;
   uint32_t wc_overflow, wc_overflow_pad_;   // memset, k_wc_check: a chunk beyond the LDS capacity
@@ -2654,13 +2596,11 @@ struct SingleEngine : Engine {
   // segmented-scan mode (default for count / sum(double|float) / avg)
   bool seg_ok = false, seg_mode = false;
   bool seg_unsafe = false;   // a non-finite or wide-range operand was seen: exact fold from then on
-  // running operand statistics of every push since reset (k_operand_stats):
+  // running operand statistics of every push since reset (k_filter_items):
   // the window can hold items of earlier pushes, so the span covers them all
   uint32_t op_emax = 0, op_emin = 0xFFFFFFFFu;
   uint32_t op_signs = 0;     // kOpNeg / kOpPos of every operand since reset
   bool seg_pref = true;      // the mode asked for (option / default), restored by reset()
-  DevBuf d_chmeta;
-  PinnedBuf h_chmeta;
   int nch = 0;                       // distinct aggregated expressions (channels)
   int ch_agg[kMaxChan] = {}, ch_type[kMaxChan] = {};
   int chan_of[kMaxAggs] = {};
@@ -2797,7 +2737,7 @@ struct SingleEngine : Engine {
   void group_attach(const std::vector<Engine*>& ms) override {
     if (grouped) throw Error(SHD_E_ARG, "the leader already belongs to a group");
     if (ms.empty() || ms.size() > 64) throw Error(SHD_E_ARG, "a group holds 1..64 member queries");
-    if (!agg_mode || !seg_mode || wkind != SHD_W_LENGTH || ngk == 0 || partitioned)
+    if (!agg_mode || !seg_mode || wkind != SHD_W_LENGTH || ngk == 0)
       throw Error(SHD_E_UNSUPPORTED, "query groups: only length-window group-by aggregates share items");
     if (counters.events != 0 || C != 0) throw Error(SHD_E_ARG, "the group leader must be fresh");
     std::vector<SingleEngine*> v;
@@ -2806,7 +2746,7 @@ struct SingleEngine : Engine {
       if (!m || m == this || m->grouped) throw Error(SHD_E_ARG, "group member: not a free window query");
       for (SingleEngine* o : v)
         if (o == m) throw Error(SHD_E_ARG, "group member listed twice");
-      bool ok = m->agg_mode && m->seg_mode && m->wkind == SHD_W_LENGTH && m->wparam <= wparam && !m->partitioned &&
+      bool ok = m->agg_mode && m->seg_mode && m->wkind == SHD_W_LENGTH && m->wparam <= wparam &&
                 m->plan.stream_types == plan.stream_types && m->filters.size() == filters.size() &&
                 m->ngk == ngk && m->gdense == gdense && m->nagg == nagg && m->outs.size() == outs.size() &&
                 m->nch == nch;
@@ -2853,14 +2793,7 @@ struct SingleEngine : Engine {
     cur = 0;
     if (k > 0) {
       ensure_items(0, k);
-      SHD_HIP(hipMemcpyAsync(ikey[0].p, L.ikey[L.cur].as<uint64_t>() + from, k * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(its[0].p, L.its[L.cur].as<int64_t>() + from, k * 8, hipMemcpyDeviceToDevice, s));
-      for (int g = 0; g < nagg; g++) {
-        SHD_HIP(hipMemcpyAsync(iargv[0].as<uint64_t>() + g * icap[0], L.iargv[L.cur].as<uint64_t>() + g * L.icap[L.cur] +
-                               from, k * 8, hipMemcpyDeviceToDevice, s));
-        SHD_HIP(hipMemcpyAsync(iargn[0].as<uint8_t>() + g * icap[0], L.iargn[L.cur].as<uint8_t>() + g * L.icap[L.cur] +
-                               from, k, hipMemcpyDeviceToDevice, s));
-      }
+      copy_items(0, L, L.cur, from, k);
     }
     C = k;
     if (!gdense) {   // hashed group ids: the leader's dictionary assigned them
@@ -2923,9 +2856,6 @@ struct SingleEngine : Engine {
     stage_begin();
     int64_t ncalls = 0;
     stage_calls(b, ncalls);
-    d_flags.reserve(n);
-    d_cnt.reserve(n * 4);
-    d_off.reserve(n * 4);
     tot.reserve();
     if (partitioned) d_pkey.reserve(n * 8);
     FilterArgs fa{};
@@ -2938,11 +2868,13 @@ struct SingleEngine : Engine {
       fa.key_col = key_col;
       fa.key_type = key_type;
     }
-    // aggregate queries (never inside a partition here: those run on the
-    // keyed window engine) filter and build their items in one pass
-    if (agg_mode && !partitioned && !knob_on(Knob::NO_FUSED_ITEMS)) {
-      push_agg_fused(b, ncalls, n, fa);
+    // aggregate queries filter and build their items in one pass
+    if (agg_mode) {
+      push_agg(b, ncalls, n, fa);
     } else {
+      d_flags.reserve(n);
+      d_cnt.reserve(n * 4);
+      d_off.reserve(n * 4);
       const FilterArgs* d_fa = dev_args(fa);
       if (knob_on(Knob::DEBUG_ARGS)) debug_filter_args(d_fa, fa, n);
       hipLaunchKernelGGL(k_filter, dim3(grid_cover(n)), dim3(kBlock), 0, s, d_fa, n, d_flags.as<uint8_t>(),
@@ -2950,8 +2882,7 @@ struct SingleEngine : Engine {
       SHD_CHECK_LAUNCH();
       scan_exclusive_u32(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n, &tot.dev()->n_pass, d_scan, s);
       mark("filter");
-      if (!agg_mode) push_filter(b, ncalls, n);
-      else push_agg(b, ncalls, n);
+      push_filter(b, ncalls, n);
     }
     SHD_HIP(hipEventRecord(ev1, s));
     stage_end();
@@ -2961,14 +2892,11 @@ struct SingleEngine : Engine {
     counters.kernel_ns = (int64_t)(ms * 1e6);
     counters.events += n;
     // TimestampGeneratorImpl: time moves to the last call's ts if later
-    if (b.advance_time || true) {
-      int64_t last = 0;
-      h_last.reserve(8);
-      SHD_HIP(hipMemcpyAsync(h_last.p, d_now.as<int64_t>() + (ncalls - 1), 8, hipMemcpyDeviceToHost, stream));
-      SHD_HIP(hipStreamSynchronize(stream));
-      last = *h_last.as<int64_t>();
-      if (last > now) now = last;
-    }
+    h_last.reserve(8);
+    SHD_HIP(hipMemcpyAsync(h_last.p, d_now.as<int64_t>() + (ncalls - 1), 8, hipMemcpyDeviceToHost, stream));
+    SHD_HIP(hipStreamSynchronize(stream));
+    const int64_t last = *h_last.as<int64_t>();
+    if (last > now) now = last;
     seq += n;
     for (SingleEngine* q : wmembers)
       if (now > q->now) q->now = now;
@@ -3049,6 +2977,57 @@ struct SingleEngine : Engine {
     counters.matches += m;
   }
 
+  // ---- the plan's outputs, aggregators and channels into a kernel's argument struct
+  // single-instruction outputs are decoded here (EmitArgs::okind)
+  template <class A>
+  void fill_outputs(A& a) const {
+    a.nout = (int)outs.size();
+    for (size_t c = 0; c < outs.size(); c++) {
+      a.outs[c] = dexpr(outs[c]);
+      const auto& code = plan.exprs[outs[c]];
+      a.okind[c] = 0;
+      if (code.size() == 1 && code[0].op == SHD_OP_LOAD) {
+        a.okind[c] = 1;
+        a.oarg[c] = code[0].c & 0xFFFF;
+      } else if (code.size() == 1 && code[0].op == SHD_OP_AGG && code[0].a >= 0 && code[0].a < nagg) {
+        a.okind[c] = 2;
+        a.oarg[c] = code[0].a;
+      }
+    }
+  }
+  template <class A>
+  void fill_aggs(A& a) const {
+    a.nagg = nagg;
+    for (int g = 0; g < nagg; g++) {
+      a.kind[g] = plan.aggs[g].kind;
+      a.type[g] = plan.aggs[g].type;
+      if constexpr (has_chan<A>::value) a.chan[g] = chan_of[g];
+    }
+  }
+  // (a query of count() alone scans one unused double channel)
+  template <class A>
+  void fill_channels(A& a) const {
+    a.nch = std::max(nch, 1);
+    for (int c = 0; c < a.nch; c++) {
+      a.ch_agg[c] = nch ? ch_agg[c] : 0;
+      a.ch_type[c] = nch ? ch_type[c] : SHD_T_DOUBLE;
+    }
+  }
+
+  // items [from, from + count) of engine `src`'s slot `sslot` to the front of slot `dslot`
+  void copy_items(int dslot, const SingleEngine& src, int sslot, int64_t from, int64_t count) {
+    hipStream_t s = stream;
+    const auto d2d = hipMemcpyDeviceToDevice;
+    SHD_HIP(hipMemcpyAsync(ikey[dslot].p, src.ikey[sslot].as<uint64_t>() + from, count * 8, d2d, s));
+    SHD_HIP(hipMemcpyAsync(its[dslot].p, src.its[sslot].as<int64_t>() + from, count * 8, d2d, s));
+    for (int g = 0; g < nagg; g++) {
+      SHD_HIP(hipMemcpyAsync(iargv[dslot].as<uint64_t>() + g * icap[dslot],
+                             src.iargv[sslot].as<uint64_t>() + g * src.icap[sslot] + from, count * 8, d2d, s));
+      SHD_HIP(hipMemcpyAsync(iargn[dslot].as<uint8_t>() + g * icap[dslot],
+                             src.iargn[sslot].as<uint8_t>() + g * src.icap[sslot] + from, count, d2d, s));
+    }
+  }
+
   void ensure_items(int slot, int64_t cap) {
     if (icap[slot] >= cap) return;
     int64_t nc = std::max<int64_t>(cap, 1024);
@@ -3057,10 +3036,10 @@ struct SingleEngine : Engine {
     t2.reserve(nc * 8);
     v2.reserve(std::max(nagg, 1) * nc * 8);
     n2.reserve(std::max(nagg, 1) * nc);
-    std::swap(ikey[slot].p, k2.p); std::swap(ikey[slot].cap, k2.cap);
-    std::swap(its[slot].p, t2.p); std::swap(its[slot].cap, t2.cap);
-    std::swap(iargv[slot].p, v2.p); std::swap(iargv[slot].cap, v2.cap);
-    std::swap(iargn[slot].p, n2.p); std::swap(iargn[slot].cap, n2.cap);
+    ikey[slot].swap(k2);
+    its[slot].swap(t2);
+    iargv[slot].swap(v2);
+    iargn[slot].swap(n2);
     icap[slot] = nc;
     // (old contents are only needed for the carry slot, which is copied explicitly)
   }
@@ -3086,9 +3065,9 @@ struct SingleEngine : Engine {
                              hipMemcpyDeviceToDevice, stream));
     }
     SHD_HIP(hipStreamSynchronize(stream));
-    std::swap(g_dsum.p, a.p); std::swap(g_dsum.cap, a.cap);
-    std::swap(g_lsum.p, l.p); std::swap(g_lsum.cap, l.cap);
-    std::swap(g_cnt.p, c.p); std::swap(g_cnt.cap, c.cap);
+    g_dsum.swap(a);
+    g_lsum.swap(l);
+    g_cnt.swap(c);
     g_nkeys = nk;
   }
 
@@ -3110,20 +3089,7 @@ struct SingleEngine : Engine {
     EmitArgs ea{};
     ea.cs = b.cs;
     ea.es = dset();
-    ea.nout = (int)outs.size();
-    for (size_t c = 0; c < outs.size(); c++) {
-      ea.outs[c] = dexpr(outs[c]);
-      const auto& code = plan.exprs[outs[c]];
-      ea.okind[c] = 0;
-      if (code.size() == 1 && code[0].op == SHD_OP_LOAD) {
-        ea.okind[c] = 1;
-        ea.oarg[c] = code[0].c & 0xFFFF;
-      } else if (code.size() == 1 && code[0].op == SHD_OP_AGG && code[0].a >= 0 && code[0].a < nagg) {
-        ea.okind[c] = 2;
-        ea.oarg[c] = code[0].a;
-      }
-      if (knob_on(Knob::NO_FAST_OUT)) ea.okind[c] = 0;
-    }
+    fill_outputs(ea);
     ea.nagg = nagg;
     for (int g = 0; g < nagg; g++) ea.kind[g] = plan.aggs[g].kind;
     ea.cap = cap;
@@ -3162,17 +3128,16 @@ struct SingleEngine : Engine {
     snn.reserve(total);
     se.reserve(total * 4);
     scall.reserve(total * 4);
-    if (NC <= 2 && !knob_on(Knob::SEG_UNPACKED)) {
-      constexpr int N2 = NC <= 2 ? NC : 1;
+    if constexpr (NC <= 2) {
       // packed in item order (coalesced), then one record read per sorted position
-      seg_items.reserve((size_t)total * sizeof(SegItem<N2>));
-      hipLaunchKernelGGL(k_seg_pack<N2>, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_sa,
+      seg_items.reserve((size_t)total * sizeof(SegItem<NC>));
+      hipLaunchKernelGGL(k_seg_pack<NC>, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_sa,
                          (const uint64_t*)iargv[cur].as<uint64_t>(), (const uint8_t*)iargn[cur].as<uint8_t>(),
                          (const uint32_t*)e_exp.as<uint32_t>(), (const int32_t*)icall.as<int32_t>(),
-                         (SegItem<N2>*)seg_items.as<char>());
+                         (SegItem<NC>*)seg_items.as<char>());
       SHD_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_seg_gather_packed<N2>, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_sa, sp,
-                         (const SegItem<N2>*)seg_items.as<char>(), sval.as<double>(), snn.as<uint8_t>(),
+      hipLaunchKernelGGL(k_seg_gather_packed<NC>, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_sa, sp,
+                         (const SegItem<NC>*)seg_items.as<char>(), sval.as<double>(), snn.as<uint8_t>(),
                          se.as<uint32_t>(), scall.as<int32_t>());
     } else {
       hipLaunchKernelGGL(k_seg_gather<NC>, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_sa, sp,
@@ -3186,21 +3151,20 @@ struct SingleEngine : Engine {
     tagg.reserve(nt * sizeof(SegAcc<NC>));
     segS.reserve((size_t)NC * total * sizeof(DD));
     segNN.reserve((size_t)NC * total * 4);
-    const bool lds = NC <= 2 && !knob_on(Knob::SEG_NOLDS);
-    if (lds)
-      hipLaunchKernelGGL(k_seg_tiles_lds<(NC <= 2 ? NC : 1)>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
-                         (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(),
-                         (SegAcc<(NC <= 2 ? NC : 1)>*)tagg.as<char>());
+    // one or two channels: the tiles are staged in LDS
+    if constexpr (NC <= 2)
+      hipLaunchKernelGGL(k_seg_tiles_lds<NC>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
+                         (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(), tagg.as<SegAcc<NC>>());
     else
       hipLaunchKernelGGL(k_seg_tiles<NC>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
                          (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(), tagg.as<SegAcc<NC>>());
     SHD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_seg_tilescan<NC>, dim3(1), dim3(kBlock), 0, s, tagg.as<SegAcc<NC>>(), nt);
     SHD_CHECK_LAUNCH();
-    if (lds)
-      hipLaunchKernelGGL(k_seg_apply_lds<(NC <= 2 ? NC : 1)>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
+    if constexpr (NC <= 2)
+      hipLaunchKernelGGL(k_seg_apply_lds<NC>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
                          (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(),
-                         (const SegAcc<(NC <= 2 ? NC : 1)>*)tagg.as<char>(), segS.as<DD>(), segNN.as<int32_t>());
+                         (const SegAcc<NC>*)tagg.as<SegAcc<NC>>(), segS.as<DD>(), segNN.as<int32_t>());
     else
       hipLaunchKernelGGL(k_seg_apply<NC>, dim3((unsigned)nt), dim3(kBlock), 0, s, total, sk,
                          (const double*)sval.as<double>(), (const uint8_t*)snn.as<uint8_t>(),
@@ -3224,11 +3188,7 @@ struct SingleEngine : Engine {
   bool wc_kernels(int64_t total, int G, int64_t cap, int64_t ncalls, int F, int kc, int K) {
     hipStream_t s = stream;
     SegArgs sa{};
-    sa.nch = NC;
-    for (int c = 0; c < NC; c++) {
-      sa.ch_agg[c] = nch ? ch_agg[c] : 0;
-      sa.ch_type[c] = nch ? ch_type[c] : SHD_T_DOUBLE;
-    }
+    fill_channels(sa);   // NC == sa.nch
     sa.nagg = nagg;
     sa.cap = cap;
     sa.C = C;
@@ -3237,12 +3197,7 @@ struct SingleEngine : Engine {
     wa.C = C;
     wa.total = total;
     wa.G = G;
-    wa.nagg = nagg;
-    for (int g = 0; g < nagg; g++) {
-      wa.kind[g] = plan.aggs[g].kind;
-      wa.type[g] = plan.aggs[g].type;
-      wa.chan[g] = chan_of[g];
-    }
+    fill_aggs(wa);
     wc_cp.reserve((size_t)(K + 1) * 8);
     wc_ce.reserve((size_t)(K + 1) * 8);
     wa.ikey = ikey[cur].as<uint64_t>();
@@ -3323,7 +3278,7 @@ struct SingleEngine : Engine {
   static constexpr int kCwRegionMax = 8192;
   DevBuf d_cw_citem, d_cw_clb;
   bool callwin_candidate(int64_t ncalls, int64_t total) const {
-    if (!seg_mode || ngk == 0 || partitioned || nch > kMaxChan || (wkind != SHD_W_LENGTH && wkind != SHD_W_TIME) ||
+    if (!seg_mode || ngk == 0 || nch > kMaxChan || (wkind != SHD_W_LENGTH && wkind != SHD_W_TIME) ||
         total >= (int64_t)UINT32_MAX - 1 || ncalls <= 0 || knob_on(Knob::NO_CALLWIN))
       return false;
     for (size_t c = 0; c + 1 < h_offs.size(); c++)
@@ -3367,12 +3322,6 @@ struct SingleEngine : Engine {
     else if (region <= 2048) callwin_direct_launch<NC, 2048, kCwCall>(d_ca, ncalls);
     else callwin_direct_launch<NC, kCwRegionMax, kCwCall>(d_ca, ncalls);
   }
-  // the call-window fold + the rows of every call (no run records / k_emit)
-  void agg_callwin(const Staged& b, int64_t total, int64_t cap, int64_t ncalls, int64_t X, uint32_t call,
-                   uint32_t region, uint64_t kmax) {
-    callwin_rows(*this, b, total, cap, ncalls, X, call, region, kmax, true);
-  }
-
   // The call-window rows of query `q` (this engine, or a member of its window
   // group) over this engine's items: q's window length, group tables, output
   // buffer and ids.  rows_known: k_cw_count's scan of the rows per call is
@@ -3388,17 +3337,8 @@ struct SingleEngine : Engine {
     const int64_t m = total - C;
     q.ensure_groups((int64_t)kmax + 1);
     CwArgs ca{};
-    ca.nch = std::max(q.nch, 1);
-    for (int c = 0; c < ca.nch; c++) {
-      ca.ch_agg[c] = q.nch ? q.ch_agg[c] : 0;
-      ca.ch_type[c] = q.nch ? q.ch_type[c] : SHD_T_DOUBLE;
-    }
-    ca.nagg = q.nagg;
-    for (int g = 0; g < q.nagg; g++) {
-      ca.kind[g] = q.plan.aggs[g].kind;
-      ca.type[g] = q.plan.aggs[g].type;
-      ca.chan[g] = q.chan_of[g];
-    }
+    q.fill_channels(ca);
+    q.fill_aggs(ca);
     ca.cap = cap;
     ca.C = C;
     ca.total = total;
@@ -3416,19 +3356,7 @@ struct SingleEngine : Engine {
     q.out.ensure(std::max<int64_t>(m, 1), s);
     ca.cs = b.cs;
     ca.es = q.dset();
-    ca.nout = (int)q.outs.size();
-    for (size_t c = 0; c < q.outs.size(); c++) {
-      ca.outs[c] = q.dexpr(q.outs[c]);
-      const auto& code = q.plan.exprs[q.outs[c]];
-      ca.okind[c] = 0;
-      if (code.size() == 1 && code[0].op == SHD_OP_LOAD) {
-        ca.okind[c] = 1;
-        ca.oarg[c] = code[0].c & 0xFFFF;
-      } else if (code.size() == 1 && code[0].op == SHD_OP_AGG && code[0].a >= 0 && code[0].a < q.nagg) {
-        ca.okind[c] = 2;
-        ca.oarg[c] = code[0].a;
-      }
-    }
+    q.fill_outputs(ca);
     ca.ievrow = ievrow.as<int32_t>();
     ca.row0 = q.out.count;
     ca.chunk0 = q.chunk_seq;
@@ -3445,7 +3373,7 @@ struct SingleEngine : Engine {
     ca.status = d_cw_status.as<uint64_t>();
     ca.nrows = &tot.dev()->cw_rows;
     const CwArgs* d_ca = dev_args(ca);
-    if (kmax < (uint64_t)kCwDirectG && !knob_on(Knob::CW_HASH)) {
+    if (kmax < (uint64_t)kCwDirectG) {
       // rows per call (distinct groups) -> each call's first row
       if (count_rows) {
         d_cw_cnt.reserve((size_t)ncalls * 4);
@@ -3552,17 +3480,8 @@ struct SingleEngine : Engine {
     const uint32_t* sp = in_alt ? oref_alt.as<uint32_t>() : oref.as<uint32_t>();
     mark("group_sort");
     SegArgs sa{};
-    sa.nch = std::max(nch, 1);
-    for (int c = 0; c < sa.nch; c++) {
-      sa.ch_agg[c] = nch ? ch_agg[c] : 0;
-      sa.ch_type[c] = nch ? ch_type[c] : SHD_T_DOUBLE;
-    }
-    sa.nagg = nagg;
-    for (int g = 0; g < nagg; g++) {
-      sa.kind[g] = plan.aggs[g].kind;
-      sa.type[g] = plan.aggs[g].type;
-      sa.chan[g] = chan_of[g];
-    }
+    fill_channels(sa);
+    fill_aggs(sa);
     sa.cap = cap;
     sa.C = C;
     sa.total = total;
@@ -3580,21 +3499,11 @@ struct SingleEngine : Engine {
 
   // the item slot `cur` holds the carry [0, C) and room for `total` items
   void grow_items(int64_t total) {
-    hipStream_t s = stream;
     if (total >= (int64_t)INT32_MAX) throw Error(SHD_E_CAPACITY, "window items exceed 2^31");
     if (icap[cur] < total) {
       int old = cur, nw = cur ^ 1;
       ensure_items(nw, total);
-      if (C > 0) {
-        SHD_HIP(hipMemcpyAsync(ikey[nw].p, ikey[old].p, C * 8, hipMemcpyDeviceToDevice, s));
-        SHD_HIP(hipMemcpyAsync(its[nw].p, its[old].p, C * 8, hipMemcpyDeviceToDevice, s));
-        for (int g = 0; g < nagg; g++) {
-          SHD_HIP(hipMemcpyAsync(iargv[nw].as<uint64_t>() + g * icap[nw], iargv[old].as<uint64_t>() + g * icap[old],
-                                 C * 8, hipMemcpyDeviceToDevice, s));
-          SHD_HIP(hipMemcpyAsync(iargn[nw].as<uint8_t>() + g * icap[nw], iargn[old].as<uint8_t>() + g * icap[old], C,
-                                 hipMemcpyDeviceToDevice, s));
-        }
-      }
+      if (C > 0) copy_items(nw, *this, old, 0, C);
       cur = nw;
     }
     const int64_t cap = icap[cur];
@@ -3614,7 +3523,7 @@ struct SingleEngine : Engine {
       ia.arg_col[g] = -1;
       if (ia.has_arg[g]) {
         ia.agg_arg[g] = dexpr(plan.aggs[g].expr);
-        if (!knob_on(Knob::NO_FAST_OUT)) ia.arg_col[g] = plain_load_attr(plan, plan.aggs[g].expr);
+        ia.arg_col[g] = plain_load_attr(plan, plan.aggs[g].expr);
       }
     }
     ia.ngroup = ngk;
@@ -3639,33 +3548,10 @@ struct SingleEngine : Engine {
     return ia;
   }
 
-  void push_agg(const Staged& b, int64_t ncalls, int64_t n) {
-    hipStream_t s = stream;
-    tot.fetch(&SingleTotals::n_pass, s);
-    SHD_HIP(hipStreamSynchronize(s));
-    const int64_t m = tot.host().n_pass;
-    tot.clear(&SingleTotals::op_flags, &SingleTotals::op_emax, 0, s);
-    tot.clear(&SingleTotals::op_emin, &SingleTotals::op_emin_pad_, 0xFF, s);
-    // items: carry slot `cur` already holds [0, C); build the new item set in slot `cur`
-    grow_items(C + m);
-    const int64_t cap = icap[cur];
-    const ItemArgs ia = item_args(b, std::max<int64_t>(m, 1));
-    hipLaunchKernelGGL(k_make_items, dim3(grid_cover(n)), dim3(kBlock), 0, s, dev_args(ia), n,
-                       (const uint32_t*)d_cnt.as<uint32_t>(), (const uint32_t*)d_off.as<uint32_t>(),
-                       (const int32_t*)d_call_of.as<int32_t>(), (const int64_t*)d_now.as<int64_t>(),
-                       ikey[cur].as<uint64_t>(), its[cur].as<int64_t>(), iargv[cur].as<uint64_t>(),
-                       iargn[cur].as<uint8_t>(), ievrow.as<int32_t>(), icall.as<int32_t>(), inow.as<int64_t>(), cap,
-                       &tot.dev()->op_flags);
-    SHD_CHECK_LAUNCH();
-    if (ngk && !gdense) gdict_assign(m, std::max<int64_t>(m, 1));
-    mark("window_items");
-    push_agg_tail(b, ncalls, n, m, false);
-  }
-
   // filter + items in one pass (k_filter_items); the item arrays are sized
   // for every event passing
   DevBuf d_fi_status;
-  void push_agg_fused(const Staged& b, int64_t ncalls, int64_t n, const FilterArgs& fa) {
+  void push_agg(const Staged& b, int64_t ncalls, int64_t n, const FilterArgs& fa) {
     hipStream_t s = stream;
     grow_items(C + n);
     const int64_t cap = icap[cur];
@@ -3705,16 +3591,17 @@ struct SingleEngine : Engine {
     tot.fetch(&SingleTotals::n_pass, &SingleTotals::kmax, s);
     SHD_HIP(hipStreamSynchronize(s));
     const int64_t m = tot.host().n_pass;
-    fused_kmax = tot.host().kmax;
+    new_kmax = tot.host().kmax;
     if (ngk && !gdense) gdict_assign(m, std::max<int64_t>(n, 1));
     mark("filter_items");
-    push_agg_tail(b, ncalls, n, m, true);
+    push_agg_items(b, ncalls, n, m);
   }
-  uint64_t fused_kmax = 0;     // largest group id of the push's new items (dense ids)
+  uint64_t new_kmax = 0;     // largest group id of the push's new items (dense ids)
   uint64_t kmax_seen = 0;      // largest dense group id since reset (an upper bound of the carried ones)
   bool kmax_known = true;      // false after a restore: one reduction over the items
 
-  void push_agg_tail(const Staged& b, int64_t ncalls, int64_t n, int64_t m, bool fused) {
+  // the push's m new items [C, C + m): expiry, fold, rows, carry
+  void push_agg_items(const Staged& b, int64_t ncalls, int64_t n, int64_t m) {
     hipStream_t s = stream;
     const int64_t total = C + m;
     const int64_t cap = icap[cur];
@@ -3757,38 +3644,15 @@ struct SingleEngine : Engine {
                          (const uint32_t*)e_exp.as<uint32_t>(), total, d_x);
       SHD_CHECK_LAUNCH();
     }
-    // the largest group id: dense ids of a fused push come from k_filter_items
-    // (carried ids are bounded by the running maximum)
-    const bool kmax_fused = fused && (gdense || ngk == 0) && kmax_known;
-    if (!kmax_fused) reduce_max_u64(ikey[cur].as<uint64_t>(), total, d_kmax, s);
+    // the largest group id: dense ids come from k_filter_items (carried ids
+    // are bounded by the running maximum)
+    const bool kmax_dense = (gdense || ngk == 0) && kmax_known;
+    if (!kmax_dense) reduce_max_u64(ikey[cur].as<uint64_t>(), total, d_kmax, s);
     const bool guard = seg_mode && nch > 0 && m > 0;
-    if (guard && !fused) {
-      d_chmeta.reserve(2 * kMaxChan * sizeof(int));
-      int meta[2 * kMaxChan];
-      for (int c = 0; c < nch; c++) {
-        meta[c] = ch_agg[c];
-        meta[kMaxChan + c] = ch_type[c];
-      }
-      h_chmeta.reserve(sizeof(meta));
-      std::memcpy(h_chmeta.p, meta, sizeof(meta));
-      SHD_HIP(hipMemcpyAsync(d_chmeta.p, h_chmeta.p, sizeof(meta), hipMemcpyHostToDevice, s));
-      hipLaunchKernelGGL(k_operand_stats, dim3((unsigned)std::min<int64_t>(1024, ceil_div(m, kBlock))), dim3(kBlock), 0,
-                         s, (const uint64_t*)iargv[cur].as<uint64_t>(), (const uint8_t*)iargn[cur].as<uint8_t>(), cap,
-                         C, m, nch, (const int*)d_chmeta.as<int>(), (const int*)d_chmeta.as<int>() + kMaxChan,
-                         &tot.dev()->op_flags);
-      SHD_CHECK_LAUNCH();
-    }
     const bool cw_cand = callwin_candidate(ncalls, total);
-    if (cw_cand) {
-      d_cw_citem.reserve((size_t)(ncalls + 1) * 4);
+    if (cw_cand) {   // (d_cw_citem: k_filter_items wrote it)
       d_cw_clb.reserve((size_t)std::max<int64_t>(ncalls, 1) * 4);
       tot.clear(&SingleTotals::cw_call, &SingleTotals::cw_region, 0, s);
-      if (!fused) {   // (k_filter_items wrote them)
-        hipLaunchKernelGGL(k_cw_citem, dim3(grid_for(ncalls + 1)), dim3(kBlock), 0, s,
-                           (const int64_t*)d_offs.as<int64_t>(), (const uint32_t*)d_off.as<uint32_t>(), n, m, C,
-                           (int)ncalls, d_cw_citem.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-      }
       hipLaunchKernelGGL(k_cw_regions, dim3(grid_for(ncalls)), dim3(kBlock), 0, s,
                          (const uint32_t*)e_exp.as<uint32_t>(), len_win ? wparam : (int64_t)0,
                          (const uint32_t*)d_cw_citem.as<uint32_t>(), (int)ncalls, d_cw_clb.as<uint32_t>(),
@@ -3800,7 +3664,7 @@ struct SingleEngine : Engine {
     const SingleTotals& ht = tot.host();
     const int64_t X = len_win ? std::max<int64_t>(0, total - wparam) : (int64_t)ht.n_expired;
     uint64_t kmax = ht.kmax;
-    if (kmax_fused) kmax = std::max(kmax_seen, fused_kmax);
+    if (kmax_dense) kmax = std::max(kmax_seen, new_kmax);
     kmax_seen = std::max(kmax_seen, kmax);
     kmax_known = true;
     const uint32_t cw_call = cw_cand ? ht.cw_call : 0u;
@@ -3842,8 +3706,7 @@ struct SingleEngine : Engine {
         throw NeedDissolve("query group: a call above 1024 events or a window beyond the call-window path");
       // direct-mapped group ids: one rows kernel for all members (they share
       // the calls' row counts); hashed ids: a launch per member
-      const bool multi = kmax < (uint64_t)kCwDirectG && !knob_on(Knob::CW_HASH) && !knob_on(Knob::CW_NO_MULTI) &&
-                         wkind == SHD_W_LENGTH;
+      const bool multi = kmax < (uint64_t)kCwDirectG && wkind == SHD_W_LENGTH;
       std::vector<const CwArgs*> margs;
       int mnch = 1;
       for (size_t k = 0; k < wmembers.size(); k++) {
@@ -3883,7 +3746,7 @@ struct SingleEngine : Engine {
     first.reserve(cap);
     if (total > 0 && !use_cw) SHD_HIP(hipMemsetAsync(first.p, 0, total, s));
     if (use_cw) {
-      agg_callwin(b, total, cap, ncalls, X, cw_call, cw_region, kmax);
+      callwin_rows(*this, b, total, cap, ncalls, X, cw_call, cw_region, kmax, true);
       emitted = true;
     } else if (seg_mode && total > 0) {
       if (!agg_chunked(total, kmax, cap, ncalls)) agg_segscan(total, kmax, cap);
@@ -3920,11 +3783,7 @@ struct SingleEngine : Engine {
                          (const uint32_t*)hoff.as<uint32_t>(), nops, hlist.as<uint32_t>());
       SHD_CHECK_LAUNCH();
       FoldArgs fo{};
-      fo.nagg = nagg;
-      for (int g = 0; g < nagg; g++) {
-        fo.kind[g] = plan.aggs[g].kind;
-        fo.type[g] = plan.aggs[g].type;
-      }
+      fill_aggs(fo);
       fo.cap = cap;
       fo.dsum = g_dsum.as<double>();
       fo.lsum = g_lsum.as<int64_t>();
@@ -3978,19 +3837,11 @@ struct SingleEngine : Engine {
 
   // carry: the unexpired suffix [X, total) becomes the new window contents
   void commit_carry(int64_t total, int64_t X, int64_t nops, int64_t ncalls) {
-    hipStream_t s = stream;
     int64_t keep = wkind == 0 ? 0 : total - X;
     if (keep > 0 && X > 0) {
       int nw = cur ^ 1;
       ensure_items(nw, keep);
-      SHD_HIP(hipMemcpyAsync(ikey[nw].p, ikey[cur].as<uint64_t>() + X, keep * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(its[nw].p, its[cur].as<int64_t>() + X, keep * 8, hipMemcpyDeviceToDevice, s));
-      for (int g = 0; g < nagg; g++) {
-        SHD_HIP(hipMemcpyAsync(iargv[nw].as<uint64_t>() + g * icap[nw], iargv[cur].as<uint64_t>() + g * icap[cur] + X,
-                               keep * 8, hipMemcpyDeviceToDevice, s));
-        SHD_HIP(hipMemcpyAsync(iargn[nw].as<uint8_t>() + g * icap[nw], iargn[cur].as<uint8_t>() + g * icap[cur] + X,
-                               keep, hipMemcpyDeviceToDevice, s));
-      }
+      copy_items(nw, *this, cur, X, keep);
       cur = nw;
     }
     C = keep;
@@ -4033,6 +3884,8 @@ std::unique_ptr<Engine> make_single_engine(const Plan& p, std::string& why) {
       (!p.part_keys.empty() && (needs_agg || (e->wkind != 0 && p.expired_on))))
     return make_window_x_engine(p, why);
   if (e->wkind != 0 && e->wparam <= 0 && e->wkind == SHD_W_LENGTH) { why = "length(0) window"; return nullptr; }
+  // aggregate => not partitioned: an aggregate inside a partition went to the
+  // window-x engine above, so the aggregate paths never test `partitioned`
   e->agg_mode = needs_agg;
   // segmented-scan aggregation: count(), sum(double|float), avg(numeric); one
   // channel per distinct argument expression (avg(price) and sum(price) share one)

@@ -35,23 +35,17 @@ namespace shd {
   X(LOCKSTEP, "SHD_LOCKSTEP", TRISTATE, PUSH, "pattern: lockstep walks off / on wherever they can run")               \
   X(NO_BPOS, "SHD_NO_BPOS", FLAG, PUSH, "pattern: never copy e2 attributes into position order (wins over SHD_BPOS)") \
   X(BPOS, "SHD_BPOS", FLAG, PUSH, "pattern: position-major e2 attributes whenever walks are dense")                   \
-  X(NO_APOS, "SHD_NO_APOS", FLAG, PUSH, "pattern: no position-major e1 operands next to the e2 ones")                 \
   X(NO_SPLIT, "SHD_NO_SPLIT", FLAG, PUSH, "pattern: f2 through eval_fpred per step, not split per comparison")        \
   X(NO_BLOCK_SKIP, "SHD_NO_BLOCK_SKIP", FLAG, PUSH, "pattern: walks never skip 64-position blocks (wins over SHD_BLOCK_SKIP)") \
   X(BLOCK_SKIP, "SHD_BLOCK_SKIP", FLAG, PUSH, "pattern: block skipping at any key density")                           \
   X(NO_RESUME_LIST, "SHD_NO_RESUME_LIST", FLAG, PUSH, "pattern: sparse deferred walks without the compacted list")    \
-  X(CARRY_SERIAL, "SHD_CARRY_SERIAL", FLAG, PUSH, "pattern: carry gathered per scan tile, not from the compacted open list") \
-  X(GATHER_ROWS, "SHD_GATHER_ROWS", FLAG, PUSH, "pattern: carry gather takes timestamps and keys from the rows, not the sorted arrays") \
   X(NO_IMPLICIT_KEY, "SHD_NO_IMPLICIT_KEY", FLAG, LOAD, "pattern: a key equality in f2 does not partition the plan")  \
   /* keyed_sort.hip */                                                                                                \
   X(KS_GENERIC_F1, "SHD_KS_GENERIC_F1", FLAG, PUSH, "fused sort: f1 through eval_fpred per row, not pre-decoded")     \
-  /* primitives.hip */                                                                                                \
-  X(RS_NOXCD, "SHD_RS_NOXCD", FLAG, PUSH, "radix sort: tiles in launch order, not grouped per XCD")                   \
   /* engine_nfa.hip */                                                                                                \
   X(NFA_DEBUG, "SHD_NFA_DEBUG", FLAG, LOAD, "NFA: print window-lane decisions (and phase clocks in the prof build)")  \
   X(NFA_CHUNK, "SHD_NFA_CHUNK", INT, PUSH, "NFA: window-lane chunk length in events (at least 1)")                    \
   X(NFA_HASH1_ZERO, "SHD_NFA_HASH1_ZERO", FLAG, PUSH, "NFA: zero the first window-lane state hash (forces the fallback)") \
-  X(NFA_INTERLEAVE, "SHD_NFA_INTERLEAVE", TRISTATE, LOAD, "NFA: 0 keeps each key state contiguous, not 64 interleaved") \
   X(NFA_WINDOW, "SHD_NFA_WINDOW", TRISTATE, LOAD, "NFA: 0 turns window lanes off")                                    \
   X(NFA_LIST, "SHD_NFA_LIST", INT, LOAD, "NFA: pending-list capacity per key (> 0)")                                  \
   X(NFA_PARTIALS, "SHD_NFA_PARTIALS", INT, LOAD, "NFA: partial capacity per key (> 0)")                               \
@@ -59,16 +53,10 @@ namespace shd {
   X(NFA_RECORDS, "SHD_NFA_RECORDS", INT, LOAD, "NFA: record capacity per key (> 0)")                                  \
   X(NFA_TIMERS, "SHD_NFA_TIMERS", INT, LOAD, "NFA: timer capacity per key (> 0)")                                     \
   /* engine_single.hip */                                                                                             \
-  X(NO_FUSED_ITEMS, "SHD_NO_FUSED_ITEMS", FLAG, PUSH, "aggregates: k_filter, then the items, not one fused pass")     \
   X(DEBUG_ARGS, "SHD_DEBUG_ARGS", FLAG, PUSH, "filter: print k_filter's arguments and stop before the launch")        \
-  X(NO_FAST_OUT, "SHD_NO_FAST_OUT", FLAG, PUSH, "aggregates: outputs and arguments through the interpreter")          \
-  X(SEG_UNPACKED, "SHD_SEG_UNPACKED", FLAG, PUSH, "segmented scan: operands gathered per column, not as packed records") \
-  X(SEG_NOLDS, "SHD_SEG_NOLDS", FLAG, PUSH, "segmented scan: tiles without LDS staging")                              \
   X(WCHUNK, "SHD_WCHUNK", FLAG, PUSH, "windows: the chunked walk (opt-in)")                                           \
   X(NO_WCHUNK, "SHD_NO_WCHUNK", FLAG, PUSH, "windows: never the chunked walk (wins over SHD_WCHUNK)")                 \
   X(NO_CALLWIN, "SHD_NO_CALLWIN", FLAG, PUSH, "windows: never the call-window path")                                  \
-  X(CW_HASH, "SHD_CW_HASH", FLAG, PUSH, "call windows: hashed group ids even where direct-mapped ones fit")           \
-  X(CW_NO_MULTI, "SHD_CW_NO_MULTI", FLAG, PUSH, "query groups: a rows launch per member, not one for all")            \
   X(FOLD_LANE, "SHD_FOLD_LANE", FLAG, PUSH, "group fold: one lane per group at any segment length")                   \
   X(FOLD_GENERIC, "SHD_FOLD_GENERIC", FLAG, PUSH, "group fold: the generic fold, not the sum + count one")            \
   X(EXACT_AGGREGATES, "SHD_EXACT_AGGREGATES", FLAG, LOAD, "aggregates: the in-order running fold, not segmented scans") \

@@ -7,7 +7,6 @@
 #include <cstdlib>
 
 #include "common.h"
-#include "knobs.h"
 #include "radix_tile.h"
 
 namespace shd {
@@ -126,11 +125,11 @@ void scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* 
 
 template <class K, int R, bool H>
 __global__ __launch_bounds__(kRsBlock) void k_rs_hist(const K* __restrict__ keys, int64_t n, int shift,
-                                                      uint32_t* __restrict__ hist, int nb, int xcd, K kb) {
+                                                      uint32_t* __restrict__ hist, int nb, K kb) {
   __shared__ uint32_t h[kRsWaves][256];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   for (int i = tid; i < kRsWaves * 256; i += kRsBlock) (&h[0][0])[i] = 0;
-  const int tile = xcd ? rs_tile_of(blockIdx.x, nb) : (int)blockIdx.x;
+  const int tile = rs_tile_of(blockIdx.x, nb);
   const int64_t wb = (int64_t)tile * rs_tile(R) + (int64_t)w * 64 * R;
   bool done = false;
   if constexpr (sizeof(K) == 4 && R % 4 == 0) {
@@ -221,10 +220,9 @@ __global__ __launch_bounds__(kRsBlock) void k_rs_scatter(const K* __restrict__ k
                                                          uint32_t* __restrict__ vout, uint32_t* __restrict__ wout,
                                                          int64_t n, int shift, const uint32_t* __restrict__ hist,
                                                          const uint32_t* __restrict__ offs,
-                                                         const uint32_t* __restrict__ dtotal, int nb, int xcd,
-                                                         K kb) {
+                                                         const uint32_t* __restrict__ dtotal, int nb, K kb) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int tile = xcd ? rs_tile_of(blockIdx.x, nb) : (int)blockIdx.x;
+  const int tile = rs_tile_of(blockIdx.x, nb);
   const int64_t t0 = (int64_t)tile * rs_tile(R);
   const int64_t wb = t0 + (int64_t)w * 64 * R;
   // this tile's histogram column and global digit offsets are loaded first:
@@ -264,17 +262,16 @@ static void radix_sort_run(K* keys, uint32_t* vals, uint32_t* w, K* keys_alt, ui
   uint32_t* hist = scratch.as<uint32_t>();
   uint32_t* offs = hist + nh;
   uint32_t* dtot = offs + nh;
-  const int xcd = knob_on(Knob::RS_NOXCD) ? 0 : 1;   // A/B switch for the tile order
   K* ki = keys; uint32_t* vi = vals; uint32_t* wi = w;
   K* ko = keys_alt; uint32_t* vo = vals_alt; uint32_t* wo = w_alt;
   for (int shift = shift0; shift < bits; shift += 8) {
-    hipLaunchKernelGGL((k_rs_hist<K, R, H>), dim3(nb), dim3(kRsBlock), 0, s, (const K*)ki, n, shift, hist, nb, xcd, kb);
+    hipLaunchKernelGGL((k_rs_hist<K, R, H>), dim3(nb), dim3(kRsBlock), 0, s, (const K*)ki, n, shift, hist, nb, kb);
     SHD_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_rs_digit_scan, dim3(256), dim3(kRsBlock), 0, s, (const uint32_t*)hist, nb, offs, dtot);
     SHD_CHECK_LAUNCH();
     hipLaunchKernelGGL((k_rs_scatter<K, R, P2, H>), dim3(nb), dim3(kRsBlock), 0, s, (const K*)ki, (const uint32_t*)vi,
                        (const uint32_t*)wi, ko, vo, wo, n, shift, (const uint32_t*)hist, (const uint32_t*)offs,
-                       (const uint32_t*)dtot, nb, xcd, kb);
+                       (const uint32_t*)dtot, nb, kb);
     SHD_CHECK_LAUNCH();
     std::swap(ki, ko);
     std::swap(vi, vo);

@@ -77,6 +77,22 @@ def test_segscan_one_call_per_push(hip_available):
     assert_rows_agg(dev, ora, qp, exact=False)
 
 
+def test_segscan_three_channels_one_call(hip_available):
+    """Three aggregated expressions: the per-column gather and the tile kernels
+    without LDS staging (k_seg_gather / k_seg_tiles / k_seg_apply, which serve
+    3 and 4 channels only).  All three channels are positive doubles, so the
+    range guard stays quiet; one 3000-event call per push is above the
+    call-window path's limit; 2500 + 3000 items span three scan tiles."""
+    qp, _ = compile_single_query("@app:playback " + SCHEMA +
+                                 "from S#window.length(2500) select k, sum(d) as s, sum(d * 2.0) as s2, "
+                                 "avg(d + 1.0) as a, count() as c group by k insert into O;")
+    batches = make_batches(21, 3, 3000, 7, one_call=True)
+    ora = run_oracle(qp, batches)
+    dev, _, kind = run_device(qp, batches)
+    assert kind == 2 and len(ora[2]) > 0
+    assert_rows_agg(dev, ora, qp, exact=False)
+
+
 def test_segscan_many_pushes_no_nulls(hip_available):
     qp, _ = compile_single_query("@app:playback " + SCHEMA + APPS[2][1])
     batches = make_batches(9, 12, 4_000, 300, nulls=False)

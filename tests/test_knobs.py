@@ -25,11 +25,11 @@ def registry():
 
 
 def design_rows():
-    """[(name, kind, when)] of the table in DESIGN.md's "Environment switches"."""
+    """[(name, kind, when, role)] of the table in DESIGN.md's "Environment switches"."""
     text = open(os.path.join(ROOT, "DESIGN.md")).read()
     m = re.search(r"^## [^\n]*Environment switches\n(.*?)(?=^## |\Z)", text, re.M | re.S)
     assert m, 'DESIGN.md has no "Environment switches" section'
-    return re.findall(r"^\| `(SHD_[A-Z0-9_]+)` \| (\w+) \| (\w+) \|", m.group(1), re.M)
+    return re.findall(r"^\| `(SHD_[A-Z0-9_]+)` \| (\w+) \| (\w+) \| ([^|]+?) \|", m.group(1), re.M)
 
 
 # ---------------------------------------------------------------- the parsers
@@ -98,7 +98,7 @@ def test_flag(parse, text, value):
 
 @pytest.mark.parametrize("text,value", [("0", "0"), ("1", "1"), ("", "-1"), ("on", "1")])
 def test_tristate(parse, text, value):
-    assert sorted(names_of("TRISTATE")) == ["SHD_FUSED_SORT", "SHD_LOCKSTEP", "SHD_NFA_INTERLEAVE", "SHD_NFA_WINDOW"]
+    assert sorted(names_of("TRISTATE")) == ["SHD_FUSED_SORT", "SHD_LOCKSTEP", "SHD_NFA_WINDOW"]
     expect(parse, {n: text for n in names_of("TRISTATE")}, "TRISTATE", value)
 
 
@@ -151,7 +151,7 @@ ENV_FORMS = [r"""(?:setenv|delenv)\(\s*["'](SHD_[A-Z0-9_]+)["']""",      # monke
 
 def test_every_variable_the_tests_and_scripts_set_exists():
     reg = registry()
-    python_rows = {n for n, kind, _ in design_rows() if kind == "python"}
+    python_rows = {n for n, kind, _, _ in design_rows() if kind == "python"}
     found = {}
     for top in ("tests", "scripts"):
         for path in files_under(os.path.join(ROOT, top)):
@@ -167,7 +167,12 @@ def test_every_variable_the_tests_and_scripts_set_exists():
 
 def test_design_table_matches_the_registry():
     rows = design_rows()
-    assert len({n for n, _, _ in rows}) == len(rows), "a knob is listed twice"
-    table = {n: (kind, when) for n, kind, when in rows if kind != "python"}
+    assert len({n for n, _, _, _ in rows}) == len(rows), "a knob is listed twice"
+    table = {n: (kind, when) for n, kind, when, _ in rows if kind != "python"}
     assert table == registry()
-    assert {n for n, kind, _ in rows if kind == "python"} == {"SHD_LIB", "SHD_ROUTE_TORCH", "SHD_ROUTE_SYNC"}
+    assert {n for n, kind, _, _ in rows if kind == "python"} == {"SHD_LIB", "SHD_ROUTE_TORCH", "SHD_ROUTE_SYNC"}
+    # the library keeps no A/B leftovers: a concluded experiment's losing side is deleted
+    roles = {role for _, _, _, role in rows}
+    assert roles == {"test hook", "override", "diagnostic", "A/B leftover"}, roles
+    assert {n for n, kind, _, role in rows if role == "A/B leftover" and kind != "python"} == set()
+    assert {n for n, _, _, role in rows if role == "A/B leftover"} == {"SHD_ROUTE_TORCH", "SHD_ROUTE_SYNC"}
