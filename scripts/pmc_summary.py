@@ -29,9 +29,11 @@ PEAK_GBS = 8000.0
 # kernels whose reads are dominated by row gathers (FETCH_SIZE x1); every other
 # kernel streams (x2).  k_resume_list: one lane per deferred walk, each from a
 # random sorted position, with the walk's f2 operands gathered by row (its
-# only streamed read is the list, 4 B per deferred walk)
-GATHER = ("k_gather_list", "k_project", "k_emit_pairs", "k_gather_bpos", "k_xw_gather_u64", "k_xw_gather_u32",
-          "k_resume_list")
+# only streamed read is the list, 4 B per deferred walk).  k_gather_rec
+# streams its records (16 B per open partial, so x1 undercounts them by 8 B)
+# and gathers the rows
+GATHER = ("k_gather_list", "k_gather_rec", "k_project", "k_emit_pairs", "k_gather_bpos", "k_xw_gather_u64",
+          "k_xw_gather_u32", "k_resume_list")
 
 
 def fetch_factor(kernel):

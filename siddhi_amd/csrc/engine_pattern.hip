@@ -255,6 +255,134 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan(const ScanArgs* __restr
   scan_block_reduce(steps, pruned, viol, nm, no, blk, blockIdx.x, bcnt, blockIdx.x, gridDim.x, false, nd);
 }
 
+// Records of the emitting scan (k_forward_scan_rec): a tile is cut into one
+// contiguous sub-tile per wave (tile / kSubPerTile positions, a multiple of
+// 64); the record of a position that ended PS_OPEN or PS_DEFER holds its
+// sorted key, payload, 32-bit time and position, the deferred ones flagged.
+constexpr int kSubPerTile = kBlock / 64;
+constexpr uint32_t kRecDeferred = 0x80000000u;   // positions stay below 2^28
+
+// k_forward_scan<false, false, false> that also emits what the tail of the
+// push reads again (sparse keys, plain / OR forms, 32-bit keys and times).
+// Each wave walks its sub-tile in 64-position slices in order; after a
+// slice's walks a ballot and a popcount prefix, added to the wave's running
+// count, give every open or deferred lane its slot, so a sub-tile's records
+// (rkey / rpv / rts / rpos at sub-tile start + slot) and its deferred
+// positions (dlist, likewise) are in position order with no block barrier and
+// no atomic.  A slice yields a handful of records (one position in nine on
+// P3), and storing them as they come made every store a partial line: the
+// records pass through a ring of kRecRing slots per wave in LDS (the wave
+// alone reads and writes it, in program order) and leave 64 at a time as
+// whole 256-B stores.  scnt: per sub-tile [0, nsub) open, [nsub, 2 nsub)
+// deferred, [2 nsub, 3 nsub) records.  Outcome bytes, resume positions,
+// ScanOut partials and the per-tile counts as k_forward_scan writes them.
+constexpr int kRecRing = 128;   // >= 63 waiting + 64 of one slice
+// orders the wave's own LDS writes before its reads (and the reverse)
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __restrict__ ap, int64_t n_ext,
+                                                             int64_t tile, const uint32_t* __restrict__ skey32,
+                                                             const uint32_t* __restrict__ spv,
+                                                             const int32_t* __restrict__ sts32,
+                                                             int32_t* __restrict__ match_row, uint8_t* __restrict__ pst,
+                                                             uint32_t* __restrict__ bcnt, ScanOut* __restrict__ blk,
+                                                             uint32_t* __restrict__ rkey, uint32_t* __restrict__ rpv,
+                                                             int32_t* __restrict__ rts, uint32_t* __restrict__ rpos,
+                                                             uint32_t* __restrict__ dlist, uint32_t* __restrict__ scnt) {
+  const ScanArgs& a = *ap;
+  const DExprSet es{};
+  uint64_t steps = 0, pruned = 0;
+  uint32_t viol = 0, no = 0, nd = 0;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t sub = tile / kSubPerTile;
+  const int64_t t0 = (int64_t)blockIdx.x * tile;
+  const int64_t t1 = t0 + tile < n_ext ? t0 + tile : n_ext;
+  const int64_t s0 = t0 + (int64_t)w * sub;                 // this wave's sub-tile (empty past the end)
+  const int64_t s1 = s0 + sub < t1 ? s0 + sub : t1;
+  const int64_t tbase = a.x.batch.ts[0];
+  const GlobalPos<false, false> ld{skey32, nullptr, spv, sts32, nullptr, tbase, a.partitioned};
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  uint32_t wrec = 0, wdef = 0;   // the wave's records / deferred positions so far (wave-uniform)
+  uint32_t wout = 0;             // records already stored (a multiple of 64 until the end)
+  __shared__ uint32_t ring[kSubPerTile][4][kRecRing];
+  uint32_t (*rg)[kRecRing] = ring[w];
+  // lane i stores waiting record wout + i to sub-tile slot wout + i
+  auto flush = [&](uint32_t cnt) {
+    wave_lds_order();
+    if ((uint32_t)lane < cnt) {
+      const uint32_t sl = (wout + (uint32_t)lane) & (kRecRing - 1);
+      const int64_t o = s0 + wout + lane;
+      rkey[o] = rg[0][sl];
+      rpv[o] = rg[1][sl];
+      rts[o] = (int32_t)rg[2][sl];
+      rpos[o] = rg[3][sl];
+    }
+    wave_lds_order();
+  };
+  for (int64_t c = s0; c < s1; c += 64) {
+    const int64_t p = c + lane;
+    uint8_t out = PS_NONE;
+    uint32_t pvp = 0;
+    int64_t tsi = 0;
+    uint64_t k = 0;
+    if (p < s1) {
+      uint32_t pq;
+      int64_t tq;
+      uint64_t kq = 0;
+      const int64_t q0 = p + 1 < n_ext ? p + 1 : n_ext - 1;
+      ld(p, pvp, tsi, k);
+      ld(q0, pq, tq, kq);
+      if (pv_flags(pvp) & F_CAND) {
+        int64_t q = p + 1;
+        int32_t j = -1;
+        uint32_t fm = 0;
+        int64_t ra = -1, rb = -1;
+        const uint8_t st = walk_partial<true, false, 1>(a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tsi,
+                                                        false, j, steps, viol, fm, ra, rb);
+        if (st == ST_DEFER) {
+          out = PS_DEFER;
+          match_row[p] = (int32_t)q;   // resume position (< 2^28)
+          nd++;
+        } else if (st == ST_OPEN) {
+          out = PS_OPEN;
+          no++;
+        } else if (st == ST_PRUNED) {
+          pruned++;
+        }
+      }
+      pst[p] = out;
+    }
+    const bool def = out == PS_DEFER, rec = def || out == PS_OPEN;
+    const uint64_t mrec = __ballot(rec), mdef = __ballot(def);
+    if (rec) {
+      const uint32_t sl = (wrec + (uint32_t)__popcll(mrec & below)) & (kRecRing - 1);
+      rg[0][sl] = (uint32_t)k;
+      rg[1][sl] = pvp;
+      rg[2][sl] = (uint32_t)(int32_t)(tsi - tbase);
+      rg[3][sl] = (uint32_t)p | (def ? kRecDeferred : 0u);
+    }
+    if (def) dlist[s0 + wdef + __popcll(mdef & below)] = (uint32_t)p;
+    wrec += (uint32_t)__popcll(mrec);
+    wdef += (uint32_t)__popcll(mdef);
+    if (wrec - wout >= 64) {   // wave-uniform
+      flush(64);
+      wout += 64;
+    }
+  }
+  if (wrec > wout) flush(wrec - wout);
+  if (lane == 0) {
+    const int64_t nsub = (int64_t)gridDim.x * kSubPerTile;
+    const int64_t st = (int64_t)blockIdx.x * kSubPerTile + w;
+    scnt[st] = wrec - wdef;
+    scnt[nsub + st] = wdef;
+    scnt[2 * nsub + st] = wrec;
+  }
+  scan_block_reduce(steps, pruned, viol, 0u, no, blk, blockIdx.x, bcnt, blockIdx.x, gridDim.x, false, nd);
+}
+
 // Position-major copy of the e2-side attributes the filters read (ExtRows::bpos):
 // dst column a, position p = batch row of position p (carried rows are e1
 // partials, never evaluated as e2 events).
@@ -763,7 +891,11 @@ __global__ __launch_bounds__(kBlock) void k_forward_resume(const ScanArgs* __res
 // (walk_partial from the deferred B event); a position's match / open counts
 // go to its own tile's slots, the walk counters to ScanOut partials
 // [slot0, slot0 + gridDim.x).  The list length is read on the device.
-template <bool K64, bool FAST, bool TS64>
+// SUB: dlist holds one list per sub-tile, at the sub-tile's start
+// (k_forward_scan_rec); doff is the exclusive prefix of their lengths, which
+// each thread searches for its sub-tile, and a walk that ends open adds to
+// its sub-tile's open count (sopen).
+template <bool K64, bool FAST, bool TS64, bool SUB = false>
 __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restrict__ ap, int64_t n_ext, int64_t tile,
                                                         int ntile, const uint32_t* __restrict__ skey32,
                                                         const uint64_t* __restrict__ skey64,
@@ -774,7 +906,9 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
                                                         int32_t* __restrict__ match_other, uint8_t* __restrict__ pst,
                                                         uint32_t* __restrict__ bcnt, ScanOut* __restrict__ blk,
                                                         int slot0, const uint32_t* __restrict__ dlist,
-                                                        const uint32_t* __restrict__ dcount) {
+                                                        const uint32_t* __restrict__ dcount,
+                                                        const uint32_t* __restrict__ doff, int nsub, int64_t sub,
+                                                        uint32_t* __restrict__ sopen) {
   const ScanArgs& a = *ap;
   const DExprSet es = a.es;
   uint64_t steps = 0, pruned = 0;
@@ -783,7 +917,20 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
   const GlobalPos<K64, TS64> ld{skey32, skey64, spv, sts32, sts64, tbase, a.partitioned};
   const int64_t cnt = *dcount;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * kBlock) {
-    const int64_t p = dlist[i];
+    int sti = 0;   // SUB: the position's sub-tile
+    int64_t p;
+    if (SUB) {
+      // the last sub-tile whose lists start at or before i (empty ones share an offset)
+      int lo = 0, hi = nsub;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((int64_t)doff[mid] <= i) lo = mid + 1; else hi = mid;
+      }
+      sti = lo - 1;
+      p = dlist[(int64_t)sti * sub + (i - (int64_t)doff[sti])];
+    } else {
+      p = dlist[i];
+    }
     int64_t q = match_row[p];
     uint32_t pvp, pq;
     int64_t tsi, tq;
@@ -806,7 +953,8 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
     } else if (st == ST_OPEN) {
       out = PS_OPEN | PS_PEND;   // it met a B event of its key: in the pending list now
       if (a.logical == 2) match_row[p] = and_code(fm, ra, rb);
-      atomicAdd(&bcnt[ntile + t], 1u);
+      if (SUB) atomicAdd(&sopen[sti], 1u);
+      else atomicAdd(&bcnt[ntile + t], 1u);
     } else if (st == ST_PRUNED) {
       pruned++;
     }
@@ -1349,6 +1497,47 @@ __global__ __launch_bounds__(kBlock) void k_open_list(const uint8_t* __restrict_
   }
 }
 
+// One open partial (ext row r, key kk) -> carry row o: the amask columns, seq,
+// key and pend flag; the time too unless it comes from the sorted positions
+// (sts: the caller stores it).  One uniform column table per branch (carried
+// rows / pushed rows).
+__device__ __forceinline__ void gather_open_row(const GatherArgs& a, int64_t o, int64_t r, uint64_t kk, bool sts,
+                                                bool pend_now) {
+  const ExtRows& x = a.x;
+  if (r < x.C) {
+    for (int c = 0; c < a.ncols; c++) {
+      if (!((a.amask >> c) & 1u)) continue;
+      if (c == a.key_attr) {
+        store_col(a.dcol[c], a.types[c], o, kk);
+        a.dnul[c][o] = 0;
+        continue;
+      }
+      const Val v = col_load(x.carry, r, c);
+      store_col(a.dcol[c], a.types[c], o, v.b);
+      a.dnul[c][o] = (uint8_t)v.null;
+    }
+    if (!sts) a.dts[o] = gld(x.carry.ts, r);
+    a.dseq[o] = x.carry_seq[r];
+  } else {
+    const int64_t br = r - x.C;
+    for (int c = 0; c < a.ncols; c++) {
+      if (!((a.amask >> c) & 1u)) continue;
+      if (c == a.key_attr) {
+        store_col(a.dcol[c], a.types[c], o, kk);
+        a.dnul[c][o] = 0;
+        continue;
+      }
+      const Val v = col_load(x.batch, br, c);
+      store_col(a.dcol[c], a.types[c], o, v.b);
+      a.dnul[c][o] = (uint8_t)v.null;
+    }
+    if (!sts) a.dts[o] = gld(x.batch.ts, br);
+    a.dseq[o] = x.seq0 + br;
+  }
+  a.dkey[o] = kk;
+  a.dpend[o] = (uint8_t)((pend_now || (r < x.C && a.pend_old[r])) ? 1 : 0);
+}
+
 __global__ __launch_bounds__(kBlock) void k_gather_list(const GatherArgs* __restrict__ ap,
                                                         const uint32_t* __restrict__ olist, int64_t n_open,
                                                         const uint8_t* __restrict__ pst,
@@ -1361,42 +1550,56 @@ __global__ __launch_bounds__(kBlock) void k_gather_list(const GatherArgs* __rest
     const int64_t p = olist[oi];
     const int64_t o = oi;
     const int64_t r = pv_row(spv[p]);
-    // one uniform column table per branch (carried rows / pushed rows)
     const uint64_t kk = !a.partitioned ? 0 : (a.key64 ? skey64[p] : (uint64_t)skey32[p]);
     const bool sts = a.sts32 || a.sts64;
-    if (r < x.C) {
-      for (int c = 0; c < a.ncols; c++) {
-        if (!((a.amask >> c) & 1u)) continue;
-        if (c == a.key_attr) {
-          store_col(a.dcol[c], a.types[c], o, kk);
-          a.dnul[c][o] = 0;
-          continue;
-        }
-        const Val v = col_load(x.carry, r, c);
-        store_col(a.dcol[c], a.types[c], o, v.b);
-        a.dnul[c][o] = (uint8_t)v.null;
-      }
-      if (!sts) a.dts[o] = gld(x.carry.ts, r);
-      a.dseq[o] = x.carry_seq[r];
-    } else {
-      const int64_t br = r - x.C;
-      for (int c = 0; c < a.ncols; c++) {
-        if (!((a.amask >> c) & 1u)) continue;
-        if (c == a.key_attr) {
-          store_col(a.dcol[c], a.types[c], o, kk);
-          a.dnul[c][o] = 0;
-          continue;
-        }
-        const Val v = col_load(x.batch, br, c);
-        store_col(a.dcol[c], a.types[c], o, v.b);
-        a.dnul[c][o] = (uint8_t)v.null;
-      }
-      if (!sts) a.dts[o] = gld(x.batch.ts, br);
-      a.dseq[o] = x.seq0 + br;
-    }
+    gather_open_row(a, o, r, kk, sts, (pst[p] & PS_PEND) != 0);
     if (sts) a.dts[o] = a.sts64 ? a.sts64[p] : gld(x.batch.ts, 0) + (int64_t)a.sts32[p];
-    a.dkey[o] = kk;
-    a.dpend[o] = (uint8_t)(((pst[p] & PS_PEND) || (r < x.C && a.pend_old[r])) ? 1 : 0);
+  }
+}
+
+// The carry gather from the scan's records (k_forward_scan_rec): one wave per
+// sub-tile walks its records in 64-record slices.  A record without the
+// deferred flag is an open partial; a flagged one is open iff its resumed
+// walk left PS_OPEN | PS_PEND in pst.  Carry row = the exclusive prefix of
+// the final per-sub-tile open counts (soff) + the valid records before it (a
+// ballot per slice), so the table is dense and in position order, as
+// k_open_list + k_gather_list leave it.  Key, ext row and time come from the
+// record; only the amask columns and a carried row's seq are row gathers.
+__global__ __launch_bounds__(kBlock) void k_gather_rec(const GatherArgs* __restrict__ ap, int64_t sub, int nsub,
+                                                       const uint32_t* __restrict__ rkey,
+                                                       const uint32_t* __restrict__ rpv,
+                                                       const int32_t* __restrict__ rts,
+                                                       const uint32_t* __restrict__ rpos,
+                                                       const uint32_t* __restrict__ scnt,
+                                                       const uint32_t* __restrict__ soff,
+                                                       const uint8_t* __restrict__ pst) {
+  const GatherArgs& a = *ap;
+  const int lane = threadIdx.x & 63;
+  const int st = (int)blockIdx.x * kSubPerTile + (threadIdx.x >> 6);
+  const int64_t base = (int64_t)st * sub;
+  const uint32_t nrec = scnt[2 * (int64_t)nsub + st];
+  const int64_t tbase = gld(a.x.batch.ts, 0);
+  const uint64_t below = ((uint64_t)1 << lane) - 1;
+  int64_t o0 = soff[st];
+  for (uint32_t i0 = 0; i0 < nrec; i0 += 64) {
+    const uint32_t i = i0 + lane;
+    bool valid = false, pend = false;
+    if (i < nrec) {
+      const uint32_t rp = rpos[base + i];
+      valid = true;
+      if (rp & kRecDeferred) {
+        const uint8_t ps = pst[rp & ~kRecDeferred];
+        valid = (ps & 0x7Fu) == PS_OPEN;
+        pend = (ps & PS_PEND) != 0;
+      }
+    }
+    const uint64_t mv = __ballot(valid);
+    if (valid) {
+      const int64_t o = o0 + __popcll(mv & below);
+      gather_open_row(a, o, pv_row(rpv[base + i]), a.partitioned ? (uint64_t)rkey[base + i] : 0, true, pend);
+      a.dts[o] = tbase + (int64_t)rts[base + i];
+    }
+    o0 += __popcll(mv);
   }
 }
 
@@ -1570,6 +1773,15 @@ struct PatternEngine : Engine {
   // sorted times of this push's positions (finish: carried partials' times)
   const int32_t* fin_sts32 = nullptr;
   const int64_t* fin_sts64 = nullptr;
+  // the scan emitted open / deferred records (k_forward_scan_rec): the free
+  // ping-pong set of the key sort holds them, finish() gathers the carry from them
+  struct ScanRecs {
+    bool on = false;
+    uint32_t *key = nullptr, *pv = nullptr, *pos = nullptr;
+    int32_t* ts = nullptr;
+    int64_t sub = 0;
+    int nsub = 0;
+  } fin_rec;
   // scratch
   DevBuf d_k32, d_k32_alt, d_k64, d_k64_alt, d_pv, d_pv_alt, d_ts, d_ts_alt, d_ts64, d_match, d_pst, d_bcnt, d_boff, d_pj,
       d_pi, d_pj_alt, d_pi_alt, d_sort, d_scan, d_blk, d_mother, d_se1, d_sot, d_olist, d_dlist;
@@ -1811,6 +2023,7 @@ struct PatternEngine : Engine {
     if (b.n <= 0) return;
     fin_sts32 = nullptr;
     fin_sts64 = nullptr;
+    fin_rec = ScanRecs{};
     sort_push(b);
   }
 
@@ -1950,6 +2163,7 @@ struct PatternEngine : Engine {
     // per-key one: pushed rows time-ordered, carried partials before them
     const bool grouped = partitioned || (implicit_key && !pg.unmono && (C == 0 || pg.carry_tmax <= pg.ts_min));
     uint32_t hash_mask = 0;
+    bool sorted_alt = false;   // the sorted triples are in the _alt set
     counters.group_bits = 0;
     if (grouped) {
       // keys of this push span [kmin, kmax]: sort the offsets from kmin (a
@@ -2007,6 +2221,7 @@ struct PatternEngine : Engine {
       }
       spv = in_alt ? d_pv_alt.as<uint32_t>() : d_pv.as<uint32_t>();
       sts32 = in_alt ? d_ts_alt.as<int32_t>() : d_ts.as<int32_t>();
+      sorted_alt = in_alt;
       mark("key_sort");
       counters.group_bits = bits;
     }
@@ -2043,8 +2258,12 @@ struct PatternEngine : Engine {
     // contiguous tiles of positions per block (compaction offsets per block)
     const int64_t tile = ceil_div(ceil_div(n_ext, nblk), kBlock) * kBlock;
     const int ntile = (int)ceil_div(n_ext, tile);
-    d_bcnt.reserve((size_t)3 * ntile * 4);
-    d_boff.reserve((size_t)3 * ntile * 4);
+    // per tile: matches, open, deferred; then per sub-tile (k_forward_scan_rec): open, deferred, records
+    const int nsub = ntile * kSubPerTile;
+    d_bcnt.reserve(((size_t)3 * ntile + (size_t)3 * nsub) * 4);
+    d_boff.reserve(((size_t)3 * ntile + (size_t)3 * nsub) * 4);
+    uint32_t* d_scnt = d_bcnt.as<uint32_t>() + 3 * ntile;
+    uint32_t* d_soff = d_boff.as<uint32_t>() + 3 * ntile;
     const bool ts64 = sts64 != nullptr;
     // deferred walks are dense when a partial expects another event of its key
     // inside `within` (every event, ungrouped): E = events per `within` span / keys
@@ -2115,6 +2334,10 @@ struct PatternEngine : Engine {
     // sparse keys (MODE 0): the deferred walks from a compacted list
     // (k_resume_list) unless SHD_NO_RESUME_LIST
     const bool rlist = rmode == 0 && !lockstep && !sa.bsum && !sorted64 && !knob_on(Knob::NO_RESUME_LIST);
+    // ... and, full 32-bit keys and times in the plain / OR forms, the scan
+    // itself emits those lists and the open partials' records (k_forward_scan_rec)
+    // unless SHD_NO_SCAN_LISTS
+    const bool slists = rlist && grouped && !hash_mask && !ts64 && logical != 2 && !knob_on(Knob::NO_SCAN_LISTS);
     const int nlb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, ceil_div(n_ext, (int64_t)64 * kBlock)));
     if (sa.bsum) {
       hipLaunchKernelGGL(k_block_sum, dim3(grid_for(ceil_div(n_ext, 64) * 64, 1, 4096)), dim3(kBlock), 0, s, d_sa,
@@ -2166,6 +2389,21 @@ struct PatternEngine : Engine {
                              d_blk.as<ScanOut>());
       } else if (hash_mask) {
         if (ts64) SHD_LAUNCH_SCAN(false, true, true); else SHD_LAUNCH_SCAN(false, false, true);
+      } else if (slists) {
+        // records into the ping-pong set the key sort left free (4 B per
+        // position each, as the sorted set), positions into d_olist
+        fin_rec.on = true;
+        fin_rec.key = sorted_alt ? d_k32.as<uint32_t>() : d_k32_alt.as<uint32_t>();
+        fin_rec.pv = sorted_alt ? d_pv.as<uint32_t>() : d_pv_alt.as<uint32_t>();
+        fin_rec.ts = sorted_alt ? d_ts.as<int32_t>() : d_ts_alt.as<int32_t>();
+        d_olist.reserve((size_t)n_ext * 4);
+        d_dlist.reserve((size_t)n_ext * 4);
+        fin_rec.pos = d_olist.as<uint32_t>();
+        fin_rec.sub = tile / kSubPerTile;
+        fin_rec.nsub = nsub;
+        hipLaunchKernelGGL(k_forward_scan_rec, dim3(ntile), dim3(kBlock), 0, s, d_sa, n_ext, tile, skey32, spv, sts32,
+                           d_match.as<int32_t>(), d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(),
+                           fin_rec.key, fin_rec.pv, fin_rec.ts, fin_rec.pos, d_dlist.as<uint32_t>(), d_scnt);
       } else {
         if (ts64) SHD_LAUNCH_SCAN(false, true, false); else SHD_LAUNCH_SCAN(false, false, false);
       }
@@ -2180,6 +2418,19 @@ struct PatternEngine : Engine {
           SHD_LAUNCH_SKIP(2, 2 * ntile);
         } else if (rmode == 2) SHD_LAUNCH_SKIP(2, ntile);
         else SHD_LAUNCH_SKIP(1, ntile);
+      } else if (slists) {
+        // the scan's per-sub-tile deferred lists: a prefix over their lengths,
+        // then one lane per deferred walk
+        uint32_t* d_ndef = &agg.dev()->n_deferred;
+        scan_exclusive_u32(d_scnt + nsub, d_soff + nsub, nsub, d_ndef, d_scan, s);
+#define SHD_LAUNCH_RSUB(FAST)                                                                                      \
+  hipLaunchKernelGGL((k_resume_list<false, FAST, false, true>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile,  \
+                     ntile, skey32, skey64, spv, sts32, sts64, d_match.as<int32_t>(), d_mother.as<int32_t>(),      \
+                     d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(), ntile,                       \
+                     (const uint32_t*)d_dlist.as<uint32_t>(), (const uint32_t*)d_ndef,                             \
+                     (const uint32_t*)(d_soff + nsub), nsub, fin_rec.sub, d_scnt)
+        if (fast2) SHD_LAUNCH_RSUB(true); else SHD_LAUNCH_RSUB(false);
+#undef SHD_LAUNCH_RSUB
       } else if (rlist) {
         // sparse keys: the deferred positions compacted into a list (per-tile
         // counts from k_forward_scan), then one lane per deferred walk
@@ -2195,7 +2446,8 @@ struct PatternEngine : Engine {
   hipLaunchKernelGGL((k_resume_list<false, FAST, TS64>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile, ntile,     \
                      skey32, skey64, spv, sts32, sts64, d_match.as<int32_t>(), d_mother.as<int32_t>(),              \
                      d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(), ntile,                        \
-                     (const uint32_t*)d_dlist.as<uint32_t>(), (const uint32_t*)d_ndef)
+                     (const uint32_t*)d_dlist.as<uint32_t>(), (const uint32_t*)d_ndef, (const uint32_t*)nullptr, 0,  \
+                     (int64_t)0, (uint32_t*)nullptr)
         if (fast2) {
           if (ts64) SHD_LAUNCH_RLIST(true, true); else SHD_LAUNCH_RLIST(true, false);
         } else {
@@ -2220,8 +2472,11 @@ struct PatternEngine : Engine {
 
     // ---- per-tile compaction offsets for matches and open partials (position order)
     scan_exclusive_u32(d_bcnt.as<uint32_t>(), d_boff.as<uint32_t>(), ntile, &agg.dev()->n_match, d_scan, s);
-    scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, &agg.dev()->n_open, d_scan,
-                       s);
+    if (slists)   // open partials per sub-tile: the offsets k_gather_rec places the carry rows by
+      scan_exclusive_u32(d_scnt, d_soff, nsub, &agg.dev()->n_open, d_scan, s);
+    else
+      scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, &agg.dev()->n_open,
+                         d_scan, s);
     mark("compact");
     agg.fetch(&PatternTotals::scan, &PatternTotals::tail_, s);
     // time of the push's last event in arrival order (NeedNfa hand-over: global expiry of unpartitioned plans)
@@ -2356,14 +2611,23 @@ struct PatternEngine : Engine {
         } else {
           ga.key_attr = -1;
         }
-        d_olist.reserve((size_t)n_open * 4);
-        hipLaunchKernelGGL(k_open_list, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),
-                           (const uint32_t*)d_boff.as<uint32_t>(), n_ext, tile, d_olist.as<uint32_t>(),
-                           (uint32_t)PS_OPEN, 1);
-        SHD_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_gather_list, dim3(grid_cover((int64_t)n_open)), dim3(kBlock), 0, s, dev_args(ga),
-                           (const uint32_t*)d_olist.as<uint32_t>(), (int64_t)n_open,
-                           (const uint8_t*)d_pst.as<uint8_t>(), spv, skey32, skey64);
+        if (fin_rec.on) {
+          hipLaunchKernelGGL(k_gather_rec, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga), fin_rec.sub, fin_rec.nsub,
+                             (const uint32_t*)fin_rec.key, (const uint32_t*)fin_rec.pv, (const int32_t*)fin_rec.ts,
+                             (const uint32_t*)fin_rec.pos,
+                             (const uint32_t*)(d_bcnt.as<uint32_t>() + 3 * ntile),
+                             (const uint32_t*)(d_boff.as<uint32_t>() + 3 * ntile),
+                             (const uint8_t*)d_pst.as<uint8_t>());
+        } else {
+          d_olist.reserve((size_t)n_open * 4);
+          hipLaunchKernelGGL(k_open_list, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),
+                             (const uint32_t*)d_boff.as<uint32_t>(), n_ext, tile, d_olist.as<uint32_t>(),
+                             (uint32_t)PS_OPEN, 1);
+          SHD_CHECK_LAUNCH();
+          hipLaunchKernelGGL(k_gather_list, dim3(grid_cover((int64_t)n_open)), dim3(kBlock), 0, s, dev_args(ga),
+                             (const uint32_t*)d_olist.as<uint32_t>(), (int64_t)n_open,
+                             (const uint8_t*)d_pst.as<uint8_t>(), spv, skey32, skey64);
+        }
       } else {
         hipLaunchKernelGGL(k_gather_carry, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga),
                            (const uint8_t*)d_pst.as<uint8_t>(), (const uint32_t*)d_boff.as<uint32_t>(), spv, skey32,

@@ -39,6 +39,7 @@ namespace shd {
   X(NO_BLOCK_SKIP, "SHD_NO_BLOCK_SKIP", FLAG, PUSH, "pattern: walks never skip 64-position blocks (wins over SHD_BLOCK_SKIP)") \
   X(BLOCK_SKIP, "SHD_BLOCK_SKIP", FLAG, PUSH, "pattern: block skipping at any key density")                           \
   X(NO_RESUME_LIST, "SHD_NO_RESUME_LIST", FLAG, PUSH, "pattern: sparse deferred walks without the compacted list")    \
+  X(NO_SCAN_LISTS, "SHD_NO_SCAN_LISTS", FLAG, PUSH, "pattern: open and deferred lists by the list passes, not from the scan") \
   X(NO_IMPLICIT_KEY, "SHD_NO_IMPLICIT_KEY", FLAG, LOAD, "pattern: a key equality in f2 does not partition the plan")  \
   /* keyed_sort.hip */                                                                                                \
   X(KS_GENERIC_F1, "SHD_KS_GENERIC_F1", FLAG, PUSH, "fused sort: f1 through eval_fpred per row, not pre-decoded")     \
