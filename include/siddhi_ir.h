@@ -115,9 +115,22 @@ enum shd_handler { SHD_H_FILTER = 1, SHD_H_WINDOW = 2 };
  *   TIME_BATCH_STREAM  the same with stream.current.event
  *   TIME_LENGTH   q = window.length (TimeLengthWindowProcessor.java:139-188)
  *   EXTERNAL_TIME q = the LONG attribute holding the event time (ExternalTimeWindowProcessor.java:124-158)
+ *   EXTERNAL_TIME_BATCH  p = windowTime; q packs the rest (ExternalTimeBatchWindowProcessor.java:153-227;
+ *                 timeout is 0 or absent):
+ *                   bits 0-15   the LONG attribute holding the event time
+ *                   bits 16-17  startTime: 0 none, 1 constant, 2 attribute (SHD_ETB_START_*)
+ *                   bit  18     replaceTimestampWithBatchEndTime
+ *                   bits 24-39  startTime's reference: an index into the plan's constant table (1), or
+ *                               the LONG attribute read from a key's first event (2)
  *   LENGTH / TIME q = 0 */
 enum shd_window { SHD_W_LENGTH = 1, SHD_W_TIME = 2, SHD_W_LENGTH_BATCH = 3, SHD_W_TIME_BATCH = 4,
-                  SHD_W_TIME_LENGTH = 5, SHD_W_EXTERNAL_TIME = 6, SHD_W_TIME_BATCH_STREAM = 7 };
+                  SHD_W_TIME_LENGTH = 5, SHD_W_EXTERNAL_TIME = 6, SHD_W_TIME_BATCH_STREAM = 7,
+                  SHD_W_EXTERNAL_TIME_BATCH = 8 };
+enum shd_etb_start { SHD_ETB_START_NONE = 0, SHD_ETB_START_CONST = 1, SHD_ETB_START_ATTR = 2 };
+#define SHD_ETB_TS_COL(q) ((int)((q) & 0xFFFF))
+#define SHD_ETB_START_MODE(q) ((int)(((q) >> 16) & 3))
+#define SHD_ETB_REPLACE(q) ((int)(((q) >> 18) & 1))
+#define SHD_ETB_START_REF(q) ((int)(((q) >> 24) & 0xFFFF))
 enum shd_agg { SHD_AGG_SUM = 1, SHD_AGG_AVG = 2, SHD_AGG_COUNT = 3 };
 
 /* Output / input event types (ComplexEvent.Type). */

@@ -971,6 +971,11 @@ struct XbArgs {
   int64_t first_flush;
   const int64_t* ilast;      // carried items' ilast (lengthBatch stream mode: their batch epoch)
   int64_t chunk0;            // global id of the push's first chunk
+  // externalTimeBatch: per sorted position its trigger flag and the triggers
+  // before it (all keys), the triggers' sorted positions (nf of them)
+  const uint32_t* trig_j;
+  const uint32_t* tjx;
+  const uint32_t* tpos;
   uint64_t* aopp;
   uint64_t* eopp;
   int64_t* epoch_j;          // per sorted position: the RESET epoch its add folds in
@@ -979,7 +984,8 @@ struct XbArgs {
 };
 
 // batch window modes (WindowXEngine::bmode)
-enum : int { XB_FULL_LEN = 0, XB_FULL_TIME = 1, XB_STREAM_LEN = 2, XB_ZERO_LEN = 3, XB_STREAM_TIME = 4 };
+enum : int { XB_FULL_LEN = 0, XB_FULL_TIME = 1, XB_STREAM_LEN = 2, XB_ZERO_LEN = 3, XB_STREAM_TIME = 4,
+              XB_FULL_EXT = 5 };
 
 // lengthBatch triggers: the new item whose open-batch ordinal completes a batch
 __global__ __launch_bounds__(kBlock) void k_xb_len_trig(const XbArgs* __restrict__ ap, uint32_t* trig) {
@@ -1017,7 +1023,7 @@ __global__ __launch_bounds__(kBlock) void k_xb_opp(const XbArgs* __restrict__ ap
     uint64_t ao = kNoOpp, eo = kNoOpp;
     int64_t ep = -1, last = 0;
     bool keep = false;
-    if (mode == XB_FULL_LEN || mode == XB_FULL_TIME) {
+    if (mode == XB_FULL_LEN || mode == XB_FULL_TIME || mode == XB_FULL_EXT) {
       // full batches: [expired previous batch] RESET [batch] at each flush
       const int64_t na = xb_added_count(a.added_j, s, ck);
       if (mode == XB_FULL_LEN) {
@@ -1033,6 +1039,23 @@ __global__ __launch_bounds__(kBlock) void k_xb_opp(const XbArgs* __restrict__ ap
           const int64_t b = (j - s - na) / a.L;
           if (b < nb) ao = 2 * flush_of(b) + 1;
           if (a.expired_on && b + 1 < nb) eo = 2 * flush_of(b + 1) + 1;
+        }
+      } else if (mode == XB_FULL_EXT) {
+        // externalTimeBatch: an item's flush is its key's first trigger after
+        // it (the trigger event itself opens the next batch); the batch
+        // awaiting expiry leaves at the key's first trigger of the push
+        const int64_t r = (int64_t)a.tjx[j] + (int64_t)a.trig_j[j];   // triggers at or before j
+        auto flush_at = [&](int64_t q) -> int64_t {   // the q-th trigger's flush, if it is this key's
+          if (q >= a.nf || (int64_t)a.tpos[q] >= e) return -1;
+          return (int64_t)a.fr[a.irow[a.sp[a.tpos[q]]]];
+        };
+        const int64_t f0 = flush_at(r);
+        if (j - s < na) {
+          if (a.expired_on && f0 >= 0) eo = 2 * (uint64_t)f0 + 1;
+        } else if (f0 >= 0) {
+          ao = 2 * (uint64_t)f0 + 1;
+          const int64_t f1 = flush_at(r + 1);
+          if (a.expired_on && f1 >= 0) eo = 2 * (uint64_t)f1 + 1;
         }
       } else {
         if (j - s < na) {
@@ -1190,6 +1213,272 @@ __global__ __launch_bounds__(kBlock) void k_xb_call_items(int64_t C, int64_t m, 
   }
 }
 
+// ---------------------------------------------------------------- externalTimeBatch
+// ExternalTimeBatchWindowProcessor.java without a timeout: process :238-311,
+// initTiming :313-334, flushToOutputChunk :336-383, findEndTime :440-444,
+// cloneAppend :446-456.  A tumbling batch per partition key clocked by the
+// event's own LONG attribute ts.  Per key: startTime, endTime E and
+// lastCurrentEventTime M (the running maximum of ts, 0 before the first
+// event).  An event with ts >= E first flushes the open batch -- one chunk:
+// [previous batch EXPIRED, stamped M] RESET [batch CURRENT] -- then sets
+// E = findEndTime(M, startTime, T) and opens the next batch; any other event
+// joins the open batch.  After a key's first event its open batch is never
+// empty, so every trigger emits a chunk and the pending RESET
+// (state.resetEvent, non-null iff the open batch holds an event) needs no
+// flag of its own.  The flush of an item is its key's first trigger after it:
+// the full-batch operation encoding of lengthBatch applies (k_xb_opp).
+//
+// Where the flushes fall.  Write B(x) = findEndTime(x, start, T) and M_i for
+// the key's running maximum after event i.  Invariant: M_i < E_i (after the
+// first event E > ts = M; a non-trigger has ts < E; a trigger sets
+// E = B(M) > M).  So a trigger has ts_i >= E_{i-1} > M_{i-1}, i.e. M_i = ts_i.
+//   Claim: if M_{i-1} >= start then E_{i-1} = B(M_{i-1}), so event i triggers
+//   iff ts_i >= B(M_{i-1}) -- a test on the prefix maximum alone.
+//   Proof: for x >= start the remainder (x - start) % T is non-negative and
+//   B(x) is the first point of the grid start + kT strictly above x.  E_{i-1}
+//   is on the grid: it is start + T (no / attribute startTime) or some B(y);
+//   for y >= start that is a grid point with B(y) - T <= y, for y < start
+//   Java's truncating % gives B(y) = (first grid point >= y) + T <= start + T.
+//   In each case E_{i-1} - T <= max(y, start) <= M_{i-1} (y is an earlier
+//   maximum), and M_{i-1} < E_{i-1} by the invariant: E_{i-1} is the first
+//   grid point above M_{i-1}.  []
+// While M_{i-1} < start (a startTime ahead of the data: negative remainders,
+// batches up to 2T long) E depends on the maximum at the last trigger itself,
+// not on its grid cell, and the rule above does not hold: that stretch of a
+// key -- a prefix of its events, M never decreases -- and the key's first
+// event are walked by one lane per key (k_etb_lane); everything after it is
+// data-parallel over the segmented prefix maximum (k_etb_trig).  Timestamps
+// are taken as non-negative, which the reference's endTime = -1 sentinel
+// assumes too (a negative endTime would re-run initTiming at the next call).
+__host__ __device__ __forceinline__ int64_t etb_find_end(int64_t cur, int64_t start, int64_t T) {
+  // :440-444; C's % truncates like Java's
+  return cur + (T - (int64_t)((uint64_t)cur - (uint64_t)start) % T);
+}
+
+struct EtbArgs {
+  int64_t total, C, T, cap, nseg, seq0;
+  int ts_col, start_mode, start_col, replace;
+  int64_t start_const;
+  const uint32_t* sp;
+  const uint32_t* segid;
+  const int64_t* segS;
+  const int64_t* segCk;
+  const int64_t* pA;          // per key segment: its carried (startTime, endTime, M) at pv[pA .. pA + 3)
+  const int64_t* pB;
+  const int64_t* pv;
+  const int32_t* irow;
+  uint64_t* iattr;            // [ncols][cap]
+  uint8_t* inul;
+  int64_t* M;                 // [total] ts of the new items -> the key's running maximum
+  uint32_t* head;             // [total] segment heads
+  int64_t* E;                 // [total] endTime in force once the item is appended
+  uint32_t* trig_j;           // [total] the item triggers a flush
+  uint32_t* trig_r;           // [n] the same per batch row
+  int64_t* seg_start;         // [nseg] the key's startTime
+  int64_t* seg_end;           // [nseg] its endTime after the lane's stretch
+  int64_t* seg_j1;            // [nseg] first position the data-parallel rule decides
+};
+
+// scan input: the new items' ts; a key's first position also takes the carried M
+__global__ __launch_bounds__(kBlock) void k_etb_seed(const EtbArgs* __restrict__ ap) {
+  const EtbArgs& a = *ap;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < a.total; j = a.total) {
+    const uint32_t k = a.segid[j];
+    const uint32_t it = a.sp[j];
+    int64_t v = it >= (uint32_t)a.C ? (int64_t)a.iattr[(int64_t)a.ts_col * a.cap + it] : INT64_MIN;
+    const bool hd = j == a.segS[k];
+    if (hd) {
+      const int64_t seed = a.pB[k] - a.pA[k] == 3 ? a.pv[a.pA[k] + 2] : 0;   // lastCurrentEventTime starts at 0
+      v = v > seed ? v : seed;
+    }
+    a.M[j] = v;
+    a.head[j] = hd ? 1u : 0u;
+    a.trig_j[j] = 0u;
+    a.E[j] = 0;
+  }
+}
+
+// Segmented inclusive prefix maximum over (head flag, int64): per-tile
+// aggregates, one block over the tiles, then each tile with its carry-in.
+constexpr int kEtbTile = kBlock * 4;
+struct SegMax {
+  int64_t v;
+  uint32_t f;
+};
+__device__ __forceinline__ SegMax segmax_op(SegMax x, SegMax y) {
+  return SegMax{y.f ? y.v : (x.v > y.v ? x.v : y.v), x.f | y.f};
+}
+// inclusive scan of one value per thread, left in LDS: lv / lf [kBlock]
+__device__ __forceinline__ void block_segmax_incl(SegMax x, int64_t* lv, uint32_t* lf) {
+  const int t = threadIdx.x;
+  lv[t] = x.v;
+  lf[t] = x.f;
+  __syncthreads();
+  for (int o = 1; o < kBlock; o <<= 1) {
+    SegMax p{INT64_MIN, 0u};
+    if (t >= o) p = SegMax{lv[t - o], lf[t - o]};
+    __syncthreads();
+    if (t >= o) {
+      x = segmax_op(p, x);
+      lv[t] = x.v;
+      lf[t] = x.f;
+    }
+    __syncthreads();
+  }
+}
+// a thread's four items of its tile, folded
+__device__ __forceinline__ SegMax etb_load4(const int64_t* v, const uint32_t* f, int64_t n, int64_t b0, SegMax* x) {
+  SegMax acc{INT64_MIN, 0u};
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    x[i] = b0 + i < n ? SegMax{v[b0 + i], f[b0 + i]} : SegMax{INT64_MIN, 0u};
+    acc = segmax_op(acc, x[i]);
+  }
+  return acc;
+}
+__global__ __launch_bounds__(kBlock) void k_etb_pmax_tiles(const int64_t* v, const uint32_t* f, int64_t n, int64_t* tv,
+                                                           uint32_t* tf) {
+  __shared__ int64_t lv[kBlock];
+  __shared__ uint32_t lf[kBlock];
+  SegMax x[4];
+  const SegMax acc = etb_load4(v, f, n, (int64_t)blockIdx.x * kEtbTile + threadIdx.x * 4, x);
+  block_segmax_incl(acc, lv, lf);
+  if (threadIdx.x == 0) {
+    tv[blockIdx.x] = lv[kBlock - 1];
+    tf[blockIdx.x] = lf[kBlock - 1];
+  }
+}
+// exclusive scan of the tile aggregates, in place (the carry-in's value is all a tile needs)
+__global__ __launch_bounds__(kBlock) void k_etb_pmax_scan(int64_t* tv, const uint32_t* tf, int64_t nt) {
+  __shared__ int64_t lv[kBlock];
+  __shared__ uint32_t lf[kBlock];
+  SegMax carry{INT64_MIN, 0u};
+  for (int64_t base = 0; base < nt; base += kBlock) {
+    const int64_t i = base + threadIdx.x;
+    const SegMax x = i < nt ? SegMax{tv[i], tf[i]} : SegMax{INT64_MIN, 0u};
+    block_segmax_incl(x, lv, lf);
+    const SegMax ex = threadIdx.x > 0 ? SegMax{lv[threadIdx.x - 1], lf[threadIdx.x - 1]} : SegMax{INT64_MIN, 0u};
+    if (i < nt) tv[i] = segmax_op(carry, ex).v;
+    carry = segmax_op(carry, SegMax{lv[kBlock - 1], lf[kBlock - 1]});
+    __syncthreads();
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_etb_pmax_apply(int64_t* v, const uint32_t* f, int64_t n, const int64_t* tpre) {
+  __shared__ int64_t lv[kBlock];
+  __shared__ uint32_t lf[kBlock];
+  SegMax x[4];
+  const int64_t b0 = (int64_t)blockIdx.x * kEtbTile + threadIdx.x * 4;
+  const SegMax acc = etb_load4(v, f, n, b0, x);
+  block_segmax_incl(acc, lv, lf);
+  SegMax run{tpre[blockIdx.x], 0u};
+  if (threadIdx.x > 0) run = segmax_op(run, SegMax{lv[threadIdx.x - 1], lf[threadIdx.x - 1]});
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    run = segmax_op(run, x[i]);
+    if (b0 + i < n) v[b0 + i] = run.v;
+  }
+}
+
+// One lane per key: a new key's first event (initTiming, and the event itself:
+// with an attribute startTime it may reach endTime at once, which flushes an
+// empty batch -- no chunk -- and moves endTime), then the events met while the
+// running maximum is still below startTime.
+__global__ __launch_bounds__(kBlock) void k_etb_lane(const EtbArgs* __restrict__ ap) {
+  const EtbArgs& a = *ap;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < a.nseg; k = a.nseg) {
+    const int64_t s = a.segS[k], e = a.segS[k + 1];
+    const uint64_t* tsv = a.iattr + (int64_t)a.ts_col * a.cap;
+    int64_t j = s + a.segCk[k];
+    int64_t start = 0, E = 0;
+    if (a.pB[k] - a.pA[k] == 3) {
+      start = a.pv[a.pA[k]];
+      E = a.pv[a.pA[k] + 1];
+    } else if (j < e) {
+      const uint32_t it = a.sp[j];
+      const int64_t ts0 = (int64_t)tsv[it];
+      if (a.start_mode == SHD_ETB_START_CONST) {
+        start = a.start_const;
+        E = etb_find_end(ts0, start, a.T);
+      } else {
+        start = a.start_mode == SHD_ETB_START_ATTR ? (int64_t)a.iattr[(int64_t)a.start_col * a.cap + it] : ts0;
+        E = start + a.T;
+      }
+      if (ts0 >= E) E = etb_find_end(a.M[j], start, a.T);
+      a.E[j] = E;
+      j++;
+    }
+    while (j < e && j > s && a.M[j - 1] < start) {
+      const uint32_t it = a.sp[j];
+      if ((int64_t)tsv[it] >= E) {
+        a.trig_j[j] = 1u;
+        a.trig_r[a.irow[it]] = 1u;
+        E = etb_find_end(a.M[j], start, a.T);
+      }
+      a.E[j] = E;
+      j++;
+    }
+    a.seg_start[k] = start;
+    a.seg_end[k] = E;
+    a.seg_j1[k] = j;
+  }
+}
+
+// Every other new item: triggers iff ts >= B(M of the events before it)
+// (the claim above); endTime once it is appended is B of the maximum then.
+__global__ __launch_bounds__(kBlock) void k_etb_trig(const EtbArgs* __restrict__ ap) {
+  const EtbArgs& a = *ap;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < a.total; j = a.total) {
+    const uint32_t it = a.sp[j];
+    const uint32_t k = a.segid[j];
+    if (it < (uint32_t)a.C || j < a.seg_j1[k] || j <= a.segS[k]) continue;
+    const int64_t start = a.seg_start[k];
+    const int64_t bnd = etb_find_end(a.M[j - 1], start, a.T);
+    const bool tr = (int64_t)a.iattr[(int64_t)a.ts_col * a.cap + it] >= bnd;
+    a.E[j] = tr ? etb_find_end(a.M[j], start, a.T) : bnd;
+    if (tr) {
+      a.trig_j[j] = 1u;
+      a.trig_r[a.irow[it]] = 1u;
+    }
+  }
+}
+
+// per flush: lastCurrentEventTime at its trigger (the EXPIRED rows' timestamp) and in_seq
+__global__ __launch_bounds__(kBlock) void k_etb_flushes(const EtbArgs* __restrict__ ap, const uint32_t* fr,
+                                                        int64_t* fnow, int64_t* fseq) {
+  const EtbArgs& a = *ap;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < a.total; j = a.total) {
+    if (!a.trig_j[j]) continue;
+    const int64_t r = a.irow[a.sp[j]];
+    fnow[fr[r]] = a.M[j];
+    fseq[fr[r]] = a.seq0 + r;
+  }
+}
+
+// The keys' state for the next push (three entries per key, key order), and
+// replaceTimestampWithBatchEndTime: the appended clone's ts attribute becomes
+// the endTime in force (:446-451).
+__global__ __launch_bounds__(kBlock) void k_etb_state(const EtbArgs* __restrict__ ap, const uint64_t* ipk,
+                                                      uint64_t* dpk, int64_t* dv) {
+  const EtbArgs& a = *ap;
+  for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < a.nseg; k = a.nseg) {
+    const int64_t s = a.segS[k], e = a.segS[k + 1];
+    const uint64_t pk = ipk[a.sp[s]];
+    dpk[3 * k] = dpk[3 * k + 1] = dpk[3 * k + 2] = pk;
+    dv[3 * k] = a.seg_start[k];
+    dv[3 * k + 1] = e - 1 >= a.seg_j1[k] ? a.E[e - 1] : a.seg_end[k];
+    dv[3 * k + 2] = a.M[e - 1];
+  }
+}
+__global__ __launch_bounds__(kBlock) void k_etb_replace(const EtbArgs* __restrict__ ap) {
+  const EtbArgs& a = *ap;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < a.total; j = a.total) {
+    const uint32_t it = a.sp[j];
+    if (it < (uint32_t)a.C) continue;
+    a.iattr[(int64_t)a.ts_col * a.cap + it] = (uint64_t)a.E[j];
+    a.inul[(int64_t)a.ts_col * a.cap + it] = 0;
+  }
+}
+
 int bits_for(uint64_t v) {
   int b = 0;
   while (b < 64 && (v >> b)) b++;
@@ -1248,6 +1537,13 @@ struct WindowXEngine : Engine {
   DevBuf xb_added, xb_aopp, xb_trig, xb_fr, xb_fnow, xb_fseq, xb_bflush, xb_ccount, xb_clast, xb_epoch, xb_keep,
       xb_last, xb_cchunk, xb_cflush, xb_cepoch, op_epoch;
   int64_t tb_epoch = -1;   // stream.current.event timeBatch: global chunk id of the last flush
+  // externalTimeBatch: the packed parameters (siddhi_ir.h); each key's
+  // (startTime, endTime, lastCurrentEventTime) is carried as three entries of
+  // the pending list ppk / pv (a known key always holds its open batch, so it
+  // has a segment in every push and the list is rewritten in segment order)
+  int etb_ts_col = 0, etb_start_mode = 0, etb_start_col = 0, etb_replace = 0;
+  int64_t etb_start_const = 0;
+  DevBuf etb_M, etb_head, etb_E, etb_trigj, etb_tjx, etb_tpos, etb_tv, etb_tf, etb_seg_start, etb_seg_end, etb_seg_j1;
   // per-push scratch
   DevBuf d_offs, d_call_of, d_last, d_call_now, d_F, d_fnow, d_flags, d_cnt, d_off, d_pkey, d_start,
       d_run, d_runs_before, d_scan, d_sort, kw, kn, kh, spk, spk2, sp, sp2, head, hscan, segS, segid, segCk,
@@ -1603,7 +1899,7 @@ struct WindowXEngine : Engine {
     bool lane_ran = false;
     if (batch) {
       // ---- batch windows: flushes, opportunities, operations
-      nops = batch_operations(n, m, total, ncalls, moved, SP, nflush);
+      nops = batch_operations(n, m, total, ncalls, nseg, moved, SP, nflush);
       mark("operations");
     } else {
     // ---- expiry opportunities
@@ -1999,8 +2295,8 @@ struct WindowXEngine : Engine {
   // order: flushes, or every event / call in the stream modes), each item's
   // add / expiry chunk and RESET epoch, the operations in key-major order
   // (k_xb_ops).  Returns the operation count.
-  int64_t batch_operations(int64_t n, int64_t m, int64_t total, int ncalls, const std::vector<char>& moved,
-                           const uint32_t* SP, int64_t& nflush) {
+  int64_t batch_operations(int64_t n, int64_t m, int64_t total, int ncalls, int64_t nseg,
+                           const std::vector<char>& moved, const uint32_t* SP, int64_t& nflush) {
     hipStream_t s = stream;
     const int64_t ta = std::max<int64_t>(total, 1);
     xb_added.reserve(ta);
@@ -2056,6 +2352,8 @@ struct WindowXEngine : Engine {
         SHD_CHECK_LAUNCH();
       }
       xb.fr = xb_fr.as<uint32_t>();
+    } else if (bmode == XB_FULL_EXT) {
+      nflush = ext_flushes(n, total, nseg, SP, xb);
     } else if (bmode == XB_STREAM_LEN || bmode == XB_ZERO_LEN) {
       // an output chunk per event (its rank among the push's new items)
       nflush = m;
@@ -2178,7 +2476,7 @@ struct WindowXEngine : Engine {
       oa.aopp = xb_aopp.as<uint64_t>();
       oa.eopp = eopp.as<uint64_t>();
       oa.epoch_j = xb_epoch.as<int64_t>();
-      oa.full = bmode == XB_FULL_LEN || bmode == XB_FULL_TIME;
+      oa.full = bmode == XB_FULL_LEN || bmode == XB_FULL_TIME || bmode == XB_FULL_EXT;
       oa.opscan = opscan.as<uint32_t>();
       oa.fnow = xb_fnow.as<int64_t>();
       oa.fseq = xb_fseq.as<int64_t>();
@@ -2195,6 +2493,107 @@ struct WindowXEngine : Engine {
       SHD_CHECK_LAUNCH();
     }
     return nops;
+  }
+
+  // externalTimeBatch: where the flushes fall (k_etb_*), ranked by trigger row;
+  // the keys' carried timing for the next push.  Returns the flush count.
+  int64_t ext_flushes(int64_t n, int64_t total, int64_t nseg, const uint32_t* SP, XbArgs& xb) {
+    hipStream_t s = stream;
+    xb_trig.reserve(std::max<int64_t>(n, 1) * 4);
+    xb_fr.reserve(std::max<int64_t>(n, 1) * 4);
+    xb_fnow.reserve(std::max<int64_t>(n, 1) * 8);
+    xb_fseq.reserve(std::max<int64_t>(n, 1) * 8);
+    if (total <= 0 || nseg <= 0) return 0;
+    const int64_t nt = ceil_div(total, kEtbTile);
+    etb_M.reserve(total * 8);
+    etb_head.reserve(total * 4);
+    etb_E.reserve(total * 8);
+    etb_trigj.reserve(total * 4);
+    etb_tjx.reserve(total * 4);
+    etb_tpos.reserve(total * 4);
+    etb_tv.reserve(nt * 8);
+    etb_tf.reserve(nt * 4);
+    etb_seg_start.reserve(nseg * 8);
+    etb_seg_end.reserve(nseg * 8);
+    etb_seg_j1.reserve(nseg * 8);
+    if (n > 0) SHD_HIP(hipMemsetAsync(xb_trig.p, 0, n * 4, s));
+    EtbArgs ea{};
+    ea.total = total;
+    ea.C = C;
+    ea.T = wparam;
+    ea.cap = icap[cur];
+    ea.nseg = nseg;
+    ea.seq0 = seq;
+    ea.ts_col = etb_ts_col;
+    ea.start_mode = etb_start_mode;
+    ea.start_col = etb_start_col;
+    ea.replace = etb_replace;
+    ea.start_const = etb_start_const;
+    ea.sp = SP;
+    ea.segid = segid.as<uint32_t>();
+    ea.segS = segS.as<int64_t>();
+    ea.segCk = segCk.as<int64_t>();
+    ea.pA = pA.as<int64_t>();
+    ea.pB = pB.as<int64_t>();
+    ea.pv = pv.as<int64_t>();
+    ea.irow = irow[cur].as<int32_t>();
+    ea.iattr = iattr[cur].as<uint64_t>();
+    ea.inul = inul[cur].as<uint8_t>();
+    ea.M = etb_M.as<int64_t>();
+    ea.head = etb_head.as<uint32_t>();
+    ea.E = etb_E.as<int64_t>();
+    ea.trig_j = etb_trigj.as<uint32_t>();
+    ea.trig_r = xb_trig.as<uint32_t>();
+    ea.seg_start = etb_seg_start.as<int64_t>();
+    ea.seg_end = etb_seg_end.as<int64_t>();
+    ea.seg_j1 = etb_seg_j1.as<int64_t>();
+    const EtbArgs* d_ea = dev_args(ea);
+    hipLaunchKernelGGL(k_etb_seed, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
+    SHD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_etb_pmax_tiles, dim3((unsigned)nt), dim3(kBlock), 0, s, (const int64_t*)etb_M.as<int64_t>(),
+                       (const uint32_t*)etb_head.as<uint32_t>(), total, etb_tv.as<int64_t>(), etb_tf.as<uint32_t>());
+    SHD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_etb_pmax_scan, dim3(1), dim3(kBlock), 0, s, etb_tv.as<int64_t>(),
+                       (const uint32_t*)etb_tf.as<uint32_t>(), nt);
+    SHD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_etb_pmax_apply, dim3((unsigned)nt), dim3(kBlock), 0, s, etb_M.as<int64_t>(),
+                       (const uint32_t*)etb_head.as<uint32_t>(), total, (const int64_t*)etb_tv.as<int64_t>());
+    SHD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_etb_lane, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, d_ea);
+    SHD_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_etb_trig, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
+    SHD_CHECK_LAUNCH();
+    // flushes in trigger-row order; per key, the triggers' sorted positions
+    const int64_t nflush = n > 0 ? scan(xb_trig.as<uint32_t>(), xb_fr.as<uint32_t>(), n) : 0;
+    scan(etb_trigj.as<uint32_t>(), etb_tjx.as<uint32_t>(), total);   // the same count, in key order
+    if (nflush > 0) {
+      hipLaunchKernelGGL(k_xw_head_list, dim3(grid_cover(total)), dim3(kBlock), 0, s,
+                         (const uint32_t*)etb_trigj.as<uint32_t>(), (const uint32_t*)etb_tjx.as<uint32_t>(), total,
+                         etb_tpos.as<uint32_t>());
+      SHD_CHECK_LAUNCH();
+      hipLaunchKernelGGL(k_etb_flushes, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea,
+                         (const uint32_t*)xb_fr.as<uint32_t>(), xb_fnow.as<int64_t>(), xb_fseq.as<int64_t>());
+      SHD_CHECK_LAUNCH();
+    }
+    ppk2.reserve(nseg * 24);
+    pv2.reserve(nseg * 24);
+    hipLaunchKernelGGL(k_etb_state, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, d_ea,
+                       (const uint64_t*)ipk[cur].as<uint64_t>(), ppk2.as<uint64_t>(), pv2.as<int64_t>());
+    SHD_CHECK_LAUNCH();
+    if (etb_replace) {
+      hipLaunchKernelGGL(k_etb_replace, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
+      SHD_CHECK_LAUNCH();
+    }
+    SHD_HIP(hipStreamSynchronize(s));
+    std::swap(ppk.p, ppk2.p); std::swap(ppk.cap, ppk2.cap);
+    std::swap(pv.p, pv2.p); std::swap(pv.cap, pv2.cap);
+    np = 3 * nseg;
+    xb.fr = xb_fr.as<uint32_t>();
+    xb.nf = nflush;
+    xb.trig_j = etb_trigj.as<uint32_t>();
+    xb.tjx = etb_tjx.as<uint32_t>();
+    xb.tpos = etb_tpos.as<uint32_t>();
+    return nflush;
   }
 
   // inclusive run id of each keyed event into d_start (k_xw_ops' run_of)
@@ -2404,13 +2803,34 @@ std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why) {
   }
   if (e->filters.size() > 4) { why = "too many filters"; return nullptr; }
   if (e->wkind == SHD_W_LENGTH && e->wparam <= 0) { why = "length(0) window"; return nullptr; }
-  e->batch = e->wkind == SHD_W_LENGTH_BATCH || e->wkind == SHD_W_TIME_BATCH || e->wkind == SHD_W_TIME_BATCH_STREAM;
+  e->batch = e->wkind == SHD_W_LENGTH_BATCH || e->wkind == SHD_W_TIME_BATCH ||
+             e->wkind == SHD_W_TIME_BATCH_STREAM || e->wkind == SHD_W_EXTERNAL_TIME_BATCH;
   if (e->wkind == SHD_W_LENGTH_BATCH)
     e->bmode = e->wparam == 0 ? XB_ZERO_LEN : ((e->wparam2 & 1) ? XB_STREAM_LEN : XB_FULL_LEN);
   else if (e->wkind == SHD_W_TIME_BATCH)
     e->bmode = XB_FULL_TIME;
   else if (e->wkind == SHD_W_TIME_BATCH_STREAM)
     e->bmode = XB_STREAM_TIME;
+  if (e->wkind == SHD_W_EXTERNAL_TIME_BATCH) {
+    e->bmode = XB_FULL_EXT;
+    const int64_t q = e->wparam2;
+    e->etb_ts_col = SHD_ETB_TS_COL(q);
+    e->etb_start_mode = SHD_ETB_START_MODE(q);
+    e->etb_replace = SHD_ETB_REPLACE(q);
+    const int ref = SHD_ETB_START_REF(q);
+    auto long_col = [&](int c) { return c >= 0 && c < e->ncols && types[c] == SHD_T_LONG; };
+    if (q < 0 || !long_col(e->etb_ts_col)) { why = "externalTimeBatch timestamp attribute"; return nullptr; }
+    if (e->etb_start_mode == SHD_ETB_START_CONST) {
+      if (ref >= (int)p.consts.size()) { why = "externalTimeBatch startTime constant"; return nullptr; }
+      e->etb_start_const = (int64_t)p.consts[ref];
+    } else if (e->etb_start_mode == SHD_ETB_START_ATTR) {
+      if (!long_col(ref)) { why = "externalTimeBatch startTime attribute"; return nullptr; }
+      e->etb_start_col = ref;
+    } else if (e->etb_start_mode != SHD_ETB_START_NONE) {
+      why = "externalTimeBatch startTime mode";
+      return nullptr;
+    }
+  }
   if (e->wkind == SHD_W_EXTERNAL_TIME && (e->wparam2 < 0 || e->wparam2 >= e->ncols)) {
     why = "externalTime attribute";
     return nullptr;
@@ -2440,6 +2860,20 @@ std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why) {
     e->gk_type[g] = expr_result_type(p, e->gk_expr[g], {});
   }
   e->group = e->ngk > 0;
+  if (e->wkind == SHD_W_EXTERNAL_TIME_BATCH && e->etb_replace) {
+    // aggregator arguments and group keys are taken from the arriving event;
+    // the reference reads them from the clone whose timestamp was replaced
+    auto reads_ts = [&](int x) {
+      if (x < 0) return false;
+      for (auto& in : p.exprs[x])
+        if (in.op == SHD_OP_LOAD && (in.c & 0xFFFF) == e->etb_ts_col) return true;
+      return false;
+    };
+    bool bad = false;
+    for (auto& a : p.aggs) bad = bad || reads_ts(a.expr);
+    for (int g : p.group_by) bad = bad || reads_ts(g);
+    if (bad) { why = "externalTimeBatch: aggregating or grouping by the replaced timestamp"; return nullptr; }
+  }
   e->plain = e->ngk == 0 && e->nagg == 0;
   // state key words: (partition key, group words); none for one global state
   e->nw = e->plain ? 0 : (e->partitioned ? 1 : 0) + e->ngk;

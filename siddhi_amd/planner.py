@@ -42,6 +42,7 @@ NODE_STREAM, NODE_NEXT, NODE_EVERY, NODE_LOGICAL, NODE_COUNT = 1, 2, 3, 4, 5
 H_FILTER, H_WINDOW = 1, 2
 W_LENGTH, W_TIME, W_LENGTH_BATCH, W_TIME_BATCH, W_TIME_LENGTH, W_EXTERNAL_TIME = 1, 2, 3, 4, 5, 6
 W_TIME_BATCH_STREAM = 7
+W_EXTERNAL_TIME_BATCH = 8
 INT64_MIN = -(1 << 63)
 AGG_SUM, AGG_AVG, AGG_COUNT = 1, 2, 3
 UNKNOWN_STATE = -1
@@ -801,7 +802,8 @@ def _plan_single(app, q, dictionary, partition, extra_streams) -> QueryPlan:
     n_windows = 0
     for h in si.handlers:
         if isinstance(h, qc.Filter):
-            if any(x[0] == H_WINDOW and x[1] in (W_LENGTH_BATCH, W_TIME_BATCH, W_TIME_BATCH_STREAM)
+            if any(x[0] == H_WINDOW and x[1] in (W_LENGTH_BATCH, W_TIME_BATCH, W_TIME_BATCH_STREAM,
+                                                 W_EXTERNAL_TIME_BATCH)
                    for x in plan.handlers):
                 raise UnsupportedPlanException("a filter after a batch window is outside the hot path")
             eid, _ = ec.compile(h.expr, 0, IDX_CURRENT, want_bool=True)
@@ -810,7 +812,7 @@ def _plan_single(app, q, dictionary, partition, extra_streams) -> QueryPlan:
             n_windows += 1
             if n_windows > 1:
                 raise SiddhiAppValidationException("only one window per stream")
-            plan.handlers.append(_window_handler(h, partition is not None, m, si.stream))
+            plan.handlers.append(_window_handler(h, partition is not None, m, si.stream, plan))
     names, types = _plan_selector(plan, q, ec, [m], False)
     _plan_partition(plan, None, partition, [si.stream], app, dictionary, extra_streams)
     plan.target = q.target
@@ -819,14 +821,15 @@ def _plan_single(app, q, dictionary, partition, extra_streams) -> QueryPlan:
                      partition is not None, {si.stream: "single"})
 
 
-def _window_handler(h, partitioned: bool, meta=None, stream=None):
+def _window_handler(h, partitioned: bool, meta=None, stream=None, plan=None):
     """(H_WINDOW, kind, p, q) of a `#window.<name>(...)` handler (include/siddhi_ir.h
     shd_window).  Batch windows in both modes: full batch (expired + RESET +
     current per flush) and `stream.current.event` true (W_TIME_BATCH_STREAM,
     lengthBatch with q = 1: the current events go out as they arrive).
     Refused: `timeBatch` inside a partition (its nextEmitTime is a field of
     the processor shared by every partition key,
-    TimeBatchWindowProcessor.java:136,283-300)."""
+    TimeBatchWindowProcessor.java:136,283-300).  `externalTimeBatch` keeps all
+    of its state per key and is allowed there (_external_time_batch_handler)."""
     ps = h.params
 
     def const(i, types, what):
@@ -882,7 +885,80 @@ def _window_handler(h, partitioned: bool, meta=None, stream=None):
             raise SiddhiAppValidationException("ExternalTime window's timeStamp should be type long")
         t = int(const(1, ("int", "long"), "window.time"))
         return (H_WINDOW, W_EXTERNAL_TIME, t, names.index(v.attr))
+    if h.name == "externaltimebatch":
+        return _external_time_batch_handler(h, meta, stream, plan)
     raise UnsupportedPlanException("window %s is outside the hot path" % h.name)
+
+
+# externalTimeBatch's q word (include/siddhi_ir.h shd_window)
+ETB_START_NONE, ETB_START_CONST, ETB_START_ATTR = 0, 1, 2
+
+
+def etb_pack(ts_col: int, start_mode: int = ETB_START_NONE, start_ref: int = 0, replace: bool = False) -> int:
+    return ts_col | (start_mode << 16) | ((1 << 18) if replace else 0) | (start_ref << 24)
+
+
+def _external_time_batch_handler(h, meta, stream, plan):
+    """`externalTimeBatch(timestamp, windowTime [, startTime [, timeout [,
+    replaceTimestampWithBatchEndTime]]])`: the validation of
+    ExternalTimeBatchWindowProcessor.init (ExternalTimeBatchWindowProcessor.java:153-227).
+    A positive timeout (a second emission path driven by the app clock's
+    Scheduler, :256-275, :385-438) is refused."""
+    ps = h.params
+    if not 2 <= len(ps) <= 5:
+        raise SiddhiAppValidationException("ExternalTimeBatch window should only have two to five parameters, "
+                                           "but found %d input attributes" % len(ps))
+    names = [a for a, _ in meta.attrs]
+
+    def long_attr(v):
+        return (isinstance(v, qc.Var) and v.index is None and v.stream in (None, stream, meta.ref)
+                and v.attr in names and dict(meta.attrs)[v.attr] == T_LONG)
+
+    def const_long(v):
+        return isinstance(v, qc.Const) and v.type in ("int", "long")
+
+    if not long_attr(ps[0]):
+        raise SiddhiAppValidationException("ExternalTimeBatch window's 1st parameter timestamp should be a "
+                                           "stream attribute of type long")
+    if not const_long(ps[1]):
+        raise SiddhiAppValidationException("ExternalTimeBatch window's 2nd parameter windowTime should be a "
+                                           "constant int/long")
+    t = int(ps[1].value)
+    mode, ref = ETB_START_NONE, 0
+    start_value = None
+    if len(ps) >= 3:
+        if const_long(ps[2]):
+            mode, start_value = ETB_START_CONST, int(ps[2].value)
+        elif long_attr(ps[2]):
+            mode, ref = ETB_START_ATTR, names.index(ps[2].attr)
+        else:
+            raise SiddhiAppValidationException("ExternalTimeBatch window's 3rd parameter startTime should either be "
+                                               "a constant (of type int or long) or an attribute (of type long)")
+    timeout = 0
+    if len(ps) >= 4:
+        if not const_long(ps[3]):
+            raise SiddhiAppValidationException("ExternalTimeBatch window's 4th parameter timeout should be a "
+                                               "constant int/long")
+        timeout = int(ps[3].value)
+    replace = False
+    if len(ps) == 5:
+        if not (isinstance(ps[4], qc.Const) and ps[4].type == "bool"):
+            raise SiddhiAppValidationException("ExternalTimeBatch window's 5th parameter "
+                                               "replaceTimestampWithBatchEndTime should be a constant bool")
+        replace = bool(ps[4].value)
+    if timeout > 0:
+        raise UnsupportedPlanException("externalTimeBatch with a positive timeout (batches flushed by the app "
+                                       "clock's scheduler) is outside the hot path")
+    if t <= 0:
+        raise UnsupportedPlanException("externalTimeBatch with a windowTime of 0 or less is outside the hot path")
+    if mode == ETB_START_CONST:
+        bits = const_bits(T_LONG, start_value)
+        if bits not in plan.consts:
+            plan.consts.append(bits)
+        ref = plan.consts.index(bits)
+    if ref >= (1 << 16):
+        raise UnsupportedPlanException("externalTimeBatch: start reference beyond 16 bits")
+    return (H_WINDOW, W_EXTERNAL_TIME_BATCH, t, etb_pack(names.index(ps[0].attr), mode, ref, replace))
 
 
 def _uses_inner_stream(inp) -> bool:
