@@ -245,6 +245,21 @@ struct Engine {
     return reinterpret_cast<const T*>(arg_dev.as<char>() + off);
   }
 
+  // Launch `kernel` on the engine's stream, then the launch check.  launch:
+  // one thread per element (grid_cover(n) blocks of kBlock threads);
+  // launch_grid: `grid` blocks of kBlock threads.  The arguments convert to
+  // the kernel's own parameter types as in a plain call, so buf.as<T>() binds
+  // to a `const T*` parameter without a cast.
+  template <class... P, class... A>
+  void launch_grid(void (*kernel)(P...), unsigned grid, A&&... args) {
+    kernel<<<dim3(grid), dim3(kBlock), 0, stream>>>(std::forward<A>(args)...);
+    SHD_CHECK_LAUNCH();
+  }
+  template <class... P, class... A>
+  void launch(void (*kernel)(P...), int64_t n, A&&... args) {
+    launch_grid(kernel, grid_cover(n), std::forward<A>(args)...);
+  }
+
   // One u32 read back on the engine's stream: 4 bytes from `dev` into the
   // pinned word `pinned`, then a stream synchronise.
   uint32_t read_u32(const void* dev, uint32_t* pinned) {

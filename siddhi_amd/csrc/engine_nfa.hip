@@ -2401,8 +2401,7 @@ struct NfaEngine : Engine {
     if (old) SHD_HIP(hipMemcpyAsync(nb.p, state.p, old, hipMemcpyDeviceToDevice, stream));
     SHD_HIP(hipMemsetAsync((char*)nb.p + old, 0, (size_t)(nc / lay.W) * lay.blk - old, stream));
     SHD_HIP(hipStreamSynchronize(stream));
-    std::swap(state.p, nb.p);
-    std::swap(state.cap, nb.cap);
+    state.swap(nb);
     slot_cap = nc;
   }
 
@@ -2743,12 +2742,10 @@ struct NfaEngine : Engine {
       bk.reserve((size_t)backup_blocks * ny.blk);
       SHD_HIP(hipMemcpyAsync(bk.p, nb.p, (size_t)backup_blocks * ny.blk, hipMemcpyDeviceToDevice, stream));
       SHD_HIP(hipStreamSynchronize(stream));
-      std::swap(backup.p, bk.p);
-      std::swap(backup.cap, bk.cap);
+      backup.swap(bk);
     }
     SHD_HIP(hipStreamSynchronize(stream));
-    std::swap(state.p, nb.p);
-    std::swap(state.cap, nb.cap);
+    state.swap(nb);
     lay = ny;
   }
 

@@ -28,6 +28,7 @@
 #include "knobs.h"
 #include "gdict.h"
 #include "agg.h"
+#include "stream_kernels.h"
 
 namespace shd {
 
@@ -86,15 +87,6 @@ struct RowCtx {
 };
 
 // ---------------------------------------------------------------- calls / time
-// call_of[i] for every event; call_last_ts[c]
-__global__ void k_call_of(const int64_t* offs, int ncalls, const int64_t* ts, int32_t* call_of, int64_t* last_ts) {
-  for (int c = blockIdx.x; c < ncalls; c += gridDim.x) {
-    int64_t a = offs[c], b = offs[c + 1];
-    for (int64_t i = a + threadIdx.x; i < b; i += blockDim.x) call_of[i] = c;
-    if (threadIdx.x == 0) last_ts[c] = b > a ? ts[b - 1] : INT64_MIN;
-  }
-}
-
 // now[c] = max(now_prev, last_ts[0..c])  (TimestampGeneratorImpl only moves forward)
 // only the playback time after the push: now[ncalls - 1] = max(now_prev, every last_ts)
 __global__ __launch_bounds__(kBlock) void k_call_now_last(const int64_t* last_ts, int ncalls, int64_t now_prev,
@@ -173,22 +165,6 @@ __global__ __launch_bounds__(kBlock) void k_filter(const FilterArgs* __restrict_
     }
     flags[i] = f;
     cnt[i] = (f & 3) == 3 ? 1u : 0u;
-  }
-}
-
-// Partition runs (PartitionStreamReceiver.receive(Event[]) :189-214): a run
-// starts at the first keyed event of a call or where the key changes from the
-// previous keyed event.  run_start[i] in {0,1}; computed over keyed events.
-__global__ void k_run_starts(const uint8_t* flags, const uint64_t* pkey, const int32_t* call_of, int64_t n,
-                             uint32_t* start) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    uint32_t s = 0;
-    if (flags[i] & 2) {
-      int64_t p = i - 1;
-      while (p >= 0 && call_of[p] == call_of[i] && !(flags[p] & 2)) p--;
-      s = (p < 0 || call_of[p] != call_of[i] || pkey[p] != pkey[i]) ? 1u : 0u;
-    }
-    start[i] = s;
   }
 }
 
@@ -621,26 +597,6 @@ __global__ void k_make_ops(int64_t C, int64_t total, const uint32_t* e, const ui
       oref[idx] = (uint32_t)x | kAddBit;
     }
   }
-}
-
-__global__ void k_narrow(const uint64_t* in, uint32_t* out, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    out[i] = (uint32_t)in[i];
-}
-
-__global__ void k_gather_u64(const uint64_t* src, const uint32_t* perm, uint64_t* dst, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    dst[i] = src[perm[i]];
-}
-
-__global__ void k_seg_heads(const uint32_t* skey, int64_t n, uint32_t* head) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1u : 0u;
-}
-
-__global__ void k_head_list(const uint32_t* head, const uint32_t* hoff, int64_t n, uint32_t* hl) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    if (head[i]) hl[hoff[i]] = (uint32_t)i;
 }
 
 struct FoldArgs {

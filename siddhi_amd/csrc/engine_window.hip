@@ -47,6 +47,7 @@
 #include "engine.h"
 #include "gdict.h"
 #include "agg.h"
+#include "stream_kernels.h"
 
 namespace shd {
 
@@ -86,23 +87,25 @@ struct ItemCtx {
   __device__ __forceinline__ Val agg(int i) const { return Val{aggv[i], (int)aggn[i]}; }
 };
 
-__device__ __forceinline__ int64_t lower_bound_i64(const int64_t* a, int64_t lo, int64_t hi, int64_t v) {
+// ---------------------------------------------------------------- searches
+// First index of [lo, hi) at which pred is false (pred holds on a prefix).
+template <class I, class P>
+__device__ __forceinline__ I first_false(I lo, I hi, P pred) {
   while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1;
+    const I mid = (lo + hi) >> 1;
+    if (pred(mid)) lo = mid + 1;
     else hi = mid;
   }
   return lo;
 }
-
-// ---------------------------------------------------------------- calls
-// call_of[i] for every event; last_ts[c] (INT64_MIN for an empty call)
-__global__ void k_xw_calls(const int64_t* offs, int ncalls, const int64_t* ts, int32_t* call_of, int64_t* last_ts) {
-  const int c = blockIdx.x;
-  if (c >= ncalls) return;
-  const int64_t a = offs[c], b = offs[c + 1];
-  for (int64_t i = a + threadIdx.x; i < b; i += kBlock) call_of[i] = c;
-  if (threadIdx.x == 0) last_ts[c] = b > a ? ts[b - 1] : INT64_MIN;
+// Ascending a[lo, hi): the first index with a[i] >= v (lower) / a[i] > v (upper).
+template <class T, class I>
+__device__ __forceinline__ I lower_bound(const T* a, I lo, I hi, T v) {
+  return first_false(lo, hi, [=](I i) { return a[i] < v; });
+}
+template <class T, class I>
+__device__ __forceinline__ I upper_bound(const T* a, I lo, I hi, T v) {
+  return first_false(lo, hi, [=](I i) { return a[i] <= v; });
 }
 
 // ---------------------------------------------------------------- items
@@ -151,31 +154,48 @@ __global__ __launch_bounds__(kBlock) void k_xw_filter(const XwArgs* __restrict__
   }
 }
 
-// Partition runs (PartitionStreamReceiver.receive(Event[]) :189-214): a run
-// starts at the first keyed event of a call or where the key changes.
-__global__ __launch_bounds__(kBlock) void k_xw_run_starts(const uint8_t* flags, const uint64_t* pkey,
-                                                          const int32_t* call_of, int64_t n, uint32_t* start) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) {
-    uint32_t s = 0;
-    if (flags[i] & 2) {
-      int64_t p = i - 1;
-      while (p >= 0 && call_of[p] == call_of[i] && !(flags[p] & 2)) p--;
-      s = (p < 0 || call_of[p] != call_of[i] || pkey[p] != pkey[i]) ? 1u : 0u;
-    }
-    start[i] = s;
-  }
-}
-
-struct ItemOut {
+// The columns of a window item.  One table row each: element size, how many
+// strided sub-columns it has ([sub][cap]: one, one per attribute, one per
+// aggregator) and whether snapshots carry it (call / row only mean something
+// inside the push that added the item).  ItemStore (host) allocates, grows,
+// saves and loads by this table; ItemPtrs is one slot as the kernels see it.
+enum ItemCol { I_PK, I_TS, I_SEQ, I_SID, I_LAST, I_CALL, I_ROW, I_ATTR, I_NUL, I_ARGV, I_ARGN, kItemCols };
+enum ItemSub { SUB_ONE, SUB_ATTR, SUB_AGG, kItemSubs };
+struct ItemColDesc {
+  int size;
+  ItemSub sub;
+  bool saved;
+};
+constexpr ItemColDesc kItemCol[kItemCols] = {
+    {8, SUB_ONE, true},    // I_PK    partition key
+    {8, SUB_ONE, true},    // I_TS    event timestamp
+    {8, SUB_ONE, true},    // I_SEQ   arrival index (shd_out.in_seq)
+    {8, SUB_ONE, true},    // I_SID   aggregator state id
+    {8, SUB_ONE, true},    // I_LAST  time windows: the key's lastTimestamp; batch windows: added flag / epoch
+    {4, SUB_ONE, false},   // I_CALL  call of the push (-1: carried)
+    {4, SUB_ONE, false},   // I_ROW   batch row of the push (-1: carried)
+    {8, SUB_ATTR, true},   // I_ATTR  attributes as 64-bit payloads
+    {1, SUB_ATTR, true},   // I_NUL   their null flags
+    {8, SUB_AGG, true},    // I_ARGV  aggregator arguments
+    {1, SUB_AGG, true},    // I_ARGN  their null flags
+};
+struct ItemPtrs {   // one pointer per column, in ItemCol order
   uint64_t* pk;
   int64_t* ts;
   int64_t* seq;
+  uint64_t* sid;
+  int64_t* last;
   int32_t* call;
   int32_t* row;
   uint64_t* attr;   // [ncols][cap]
   uint8_t* nul;
   uint64_t* argv;   // [nagg][cap]
   uint8_t* argn;
+};
+static_assert(sizeof(ItemPtrs) == kItemCols * sizeof(void*), "ItemPtrs: one pointer per ItemCol");
+
+struct ItemOut {
+  ItemPtrs it;
   uint64_t* kw;     // [nw][m] state key words of the new items
   uint8_t* kn;
   uint64_t* kh;
@@ -192,21 +212,21 @@ __global__ __launch_bounds__(kBlock) void k_xw_items(const XwArgs* __restrict__ 
     const int64_t j = off[i];
     const int64_t t = a.C + j;
     BatchCtx cx{&a.cs, i};
-    o.pk[t] = pkey[i];
-    o.ts[t] = a.cs.ts[i];
-    o.seq[t] = a.seq0 + i;
-    o.call[t] = call_of[i];
-    o.row[t] = (int32_t)i;
+    o.it.pk[t] = pkey[i];
+    o.it.ts[t] = a.cs.ts[i];
+    o.it.seq[t] = a.seq0 + i;
+    o.it.call[t] = call_of[i];
+    o.it.row[t] = (int32_t)i;
     for (int c = 0; c < a.ncols; c++) {
       Val v = col_load(a.cs, i, c);
-      o.attr[(int64_t)c * a.cap + t] = v.b;
-      o.nul[(int64_t)c * a.cap + t] = (uint8_t)v.null;
+      o.it.attr[(int64_t)c * a.cap + t] = v.b;
+      o.it.nul[(int64_t)c * a.cap + t] = (uint8_t)v.null;
     }
     for (int g = 0; g < a.nagg; g++) {
       Val v{0, 1};
       if (a.has_arg[g]) v = eval_expr(a.es.ins + a.agg_arg[g].off, a.agg_arg[g].len, a.es.consts, cx);
-      o.argv[(int64_t)g * a.cap + t] = v.b;
-      o.argn[(int64_t)g * a.cap + t] = (uint8_t)v.null;
+      o.it.argv[(int64_t)g * a.cap + t] = v.b;
+      o.it.argn[(int64_t)g * a.cap + t] = (uint8_t)v.null;
     }
     if (a.nw > 0) {
       // state key: (partition key, GroupByKeyGenerator words) -- gdict.h
@@ -235,11 +255,6 @@ __global__ __launch_bounds__(kBlock) void k_xw_items(const XwArgs* __restrict__ 
 }
 
 // ---------------------------------------------------------------- segments
-__global__ __launch_bounds__(kBlock) void k_xw_seg_heads(const uint64_t* spk, int64_t total, uint32_t* head) {
-  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < total; j = total)
-    head[j] = (j == 0 || spk[j] != spk[j - 1]) ? 1u : 0u;
-}
-
 // segS[k] = first sorted position of segment k; segid[j]
 __global__ __launch_bounds__(kBlock) void k_xw_seg_list(const uint32_t* head, const uint32_t* hscan, int64_t total,
                                                         int64_t* segS, uint32_t* segid) {
@@ -268,26 +283,11 @@ __global__ __launch_bounds__(kBlock) void k_xw_seg_info(int64_t nseg, const int6
                                                         int64_t* segCk, int64_t* pA, int64_t* pB, uint32_t* proom) {
   for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < nseg; k = nseg) {
     const int64_t s = segS[k], e = segS[k + 1];
-    int64_t lo = s, hi = e;   // first position holding a new item
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (sp[mid] < (uint32_t)C) lo = mid + 1;
-      else hi = mid;
-    }
+    const int64_t lo = lower_bound(sp, s, e, (uint32_t)C);   // first position holding a new item
     segCk[k] = lo - s;
     const uint64_t pk = ipk[sp[s]];
-    int64_t a = 0, b = np;
-    while (a < b) {
-      const int64_t mid = (a + b) >> 1;
-      if (ppk[mid] < pk) a = mid + 1;
-      else b = mid;
-    }
-    int64_t c = a, d = np;
-    while (c < d) {
-      const int64_t mid = (c + d) >> 1;
-      if (ppk[mid] <= pk) c = mid + 1;
-      else d = mid;
-    }
+    const int64_t a = lower_bound(ppk, (int64_t)0, np, pk);
+    const int64_t c = upper_bound(ppk, a, np, pk);
     pA[k] = a;
     pB[k] = c;
     proom[k] = (uint32_t)((c - a) + (e - s - (lo - s)));
@@ -349,15 +349,6 @@ struct LaneArgs {
   int64_t* last_out;
 };
 
-__device__ __forceinline__ int upper_bound_call(const int32_t* F, int lo, int hi, int32_t c) {
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (F[mid] <= c) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // One lane per key segment: TimeWindowProcessor.process over the key's items
 // in arrival order, interleaved with the push's clock moves (Scheduler
 // onTimeChange -> sendTimerEvents for the key when its notify head <= now).
@@ -377,7 +368,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_time_lane(const LaneArgs* __restr
       const int32_t cy = y < e ? a.icall[a.sp[y]] : 0x7FFFFFFF;
       // clock moves before item y (its call's setCurrentTimestamp comes first)
       while (fi < a.nf && a.F[fi] <= cy) {
-        const int fe = upper_bound_call(a.F, fi, a.nf, cy);
+        const int fe = upper_bound(a.F, fi, a.nf, cy);
         int64_t hv;
         if (pc < pB) hv = a.pv[pc];
         else if (rnext >= 0) hv = a.its[a.sp[rnext]] + a.T;
@@ -385,12 +376,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_time_lane(const LaneArgs* __restr
           fi = fe;
           break;
         }
-        int lo = fi, hi = fe;   // first clock move reaching the head
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (a.fnow[mid] < hv) lo = mid + 1;
-          else hi = mid;
-        }
+        const int lo = lower_bound(a.fnow, fi, fe, hv);   // first clock move reaching the head
         if (lo == fe) {
           fi = fe;
           break;
@@ -479,12 +465,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_orphans(int64_t np, const uint64_
                                                        int64_t nseg, const uint64_t* seg_pk, int nf,
                                                        const int64_t* fnow, uint32_t* keep) {
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < np; p = np) {
-    int64_t lo = 0, hi = nseg;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (seg_pk[mid] < ppk[p]) lo = mid + 1;
-      else hi = mid;
-    }
+    const int64_t lo = lower_bound(seg_pk, (int64_t)0, nseg, ppk[p]);
     const bool has_seg = lo < nseg && seg_pk[lo] == ppk[p];
     // the key's FIFO is polled while its head <= now: entry p is gone when it
     // and every earlier entry of its key are <= the push's last clock
@@ -539,21 +520,12 @@ struct OpArgs {
   int64_t* op_seq;            // shd_out.in_seq of a row emitted at this op
 };
 
-__device__ __forceinline__ int64_t upper_bound_i32(const int32_t* a, int64_t lo, int64_t hi, int32_t v) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] <= v) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 // chunk ordinal of an item opportunity at batch row r: the event chunks (calls
 // or partition runs) and timer chunks interleave per call, timers first
 __device__ __forceinline__ uint32_t event_ordinal(const OpArgs& a, int64_t r) {
   const int32_t c = a.call_of[r];
   const int64_t ev = a.partitioned ? (int64_t)a.run_of[r] : (int64_t)c;
-  return (uint32_t)(ev + upper_bound_i32(a.sF, 0, a.nt, c));
+  return (uint32_t)(ev + upper_bound(a.sF, (int64_t)0, a.nt, c));
 }
 
 __global__ __launch_bounds__(kBlock) void k_xw_ops(const OpArgs* __restrict__ ap) {
@@ -566,12 +538,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_ops(const OpArgs* __restrict__ ap
     if (it >= (uint32_t)a.C) {   // the add (CURRENT) of a new item
       const int64_t r = a.irow[it];
       const uint64_t oy = 2ull * (uint64_t)r + 1ull;
-      int64_t lo = s, hi = j;    // expirations of this key at or before the opportunity
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.eopp[mid] <= oy) lo = mid + 1;
-        else hi = mid;
-      }
+      const int64_t lo = upper_bound(a.eopp, s, j, oy);   // expirations of this key at or before the opportunity
       const int64_t q = base + (j - s - ck) + (lo - s);
       a.op_item[q] = it;
       a.op_add[q] = 1;
@@ -582,12 +549,8 @@ __global__ __launch_bounds__(kBlock) void k_xw_ops(const OpArgs* __restrict__ ap
     }
     const uint64_t o = a.eopp[j];
     if (o != kNoOpp) {           // the EXPIRED event of item j
-      int64_t lo = s + ck, hi = e;   // adds of this key before the opportunity
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (2ull * (uint64_t)a.irow[a.sp[mid]] + 1ull < o) lo = mid + 1;
-        else hi = mid;
-      }
+      // adds of this key before the opportunity
+      const int64_t lo = first_false(s + ck, e, [&](int64_t i) { return 2ull * (uint64_t)a.irow[a.sp[i]] + 1ull < o; });
       const int64_t q = base + (j - s) + (lo - s - ck);
       a.op_item[q] = it;
       a.op_add[q] = 0;
@@ -828,10 +791,7 @@ struct CarryArgs {
   const uint32_t* segid;
   const int64_t* last_out;   // per segment (time windows), may be null
   const int64_t* last_j;     // batch windows: per sorted position, its ilast in the carry
-  const uint64_t* pk; const int64_t* ts; const int64_t* seq; const uint64_t* sid;
-  const uint64_t* attr; const uint8_t* nul; const uint64_t* argv; const uint8_t* argn;
-  uint64_t* d_pk; int64_t* d_ts; int64_t* d_seq; uint64_t* d_sid; int64_t* d_last; int32_t* d_call; int32_t* d_row;
-  uint64_t* d_attr; uint8_t* d_nul; uint64_t* d_argv; uint8_t* d_argn;
+  ItemPtrs src, dst;
 };
 
 // The kept items, in sorted (key, FIFO) order, become the next push's carry.
@@ -841,20 +801,20 @@ __global__ __launch_bounds__(kBlock) void k_xw_carry(const CarryArgs* __restrict
     if (!a.keep[j]) continue;
     const int64_t t = a.koff[j];
     const uint32_t it = a.sp[j];
-    a.d_pk[t] = a.pk[it];
-    a.d_ts[t] = a.ts[it];
-    a.d_seq[t] = a.seq[it];
-    a.d_sid[t] = a.sid[it];
-    a.d_last[t] = a.last_j ? a.last_j[j] : (a.last_out ? a.last_out[a.segid[j]] : INT64_MIN);
-    a.d_call[t] = -1;
-    a.d_row[t] = -1;
+    a.dst.pk[t] = a.src.pk[it];
+    a.dst.ts[t] = a.src.ts[it];
+    a.dst.seq[t] = a.src.seq[it];
+    a.dst.sid[t] = a.src.sid[it];
+    a.dst.last[t] = a.last_j ? a.last_j[j] : (a.last_out ? a.last_out[a.segid[j]] : INT64_MIN);
+    a.dst.call[t] = -1;
+    a.dst.row[t] = -1;
     for (int c = 0; c < a.ncols; c++) {
-      a.d_attr[(int64_t)c * a.cap_dst + t] = a.attr[(int64_t)c * a.cap_src + it];
-      a.d_nul[(int64_t)c * a.cap_dst + t] = a.nul[(int64_t)c * a.cap_src + it];
+      a.dst.attr[(int64_t)c * a.cap_dst + t] = a.src.attr[(int64_t)c * a.cap_src + it];
+      a.dst.nul[(int64_t)c * a.cap_dst + t] = a.src.nul[(int64_t)c * a.cap_src + it];
     }
     for (int g = 0; g < a.nagg; g++) {
-      a.d_argv[(int64_t)g * a.cap_dst + t] = a.argv[(int64_t)g * a.cap_src + it];
-      a.d_argn[(int64_t)g * a.cap_dst + t] = a.argn[(int64_t)g * a.cap_src + it];
+      a.dst.argv[(int64_t)g * a.cap_dst + t] = a.src.argv[(int64_t)g * a.cap_src + it];
+      a.dst.argn[(int64_t)g * a.cap_dst + t] = a.src.argn[(int64_t)g * a.cap_src + it];
     }
   }
 }
@@ -882,6 +842,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_pend_orphan_copy(int64_t np, cons
   }
 }
 
+// k_gather_u64 with the values' sign bit flipped (signed -> order-preserving unsigned)
 __global__ __launch_bounds__(kBlock) void k_xw_gather_u64(const uint64_t* src, const uint32_t* perm, uint64_t* dst,
                                                           int64_t n, uint64_t flip) {
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) dst[i] = src[perm[i]] ^ flip;
@@ -897,24 +858,9 @@ __global__ __launch_bounds__(kBlock) void k_xw_timer_rank(const uint32_t* perm, 
     sF[t] = tF[perm[t]];
   }
 }
-__global__ __launch_bounds__(kBlock) void k_xw_narrow(const uint64_t* in, uint32_t* out, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) out[i] = (uint32_t)in[i];
-}
 __global__ __launch_bounds__(kBlock) void k_xw_op_sid(int64_t nops, const uint32_t* op_item, const uint64_t* isid,
                                                       uint32_t* out) {
   for (int64_t q = (int64_t)blockIdx.x * kBlock + threadIdx.x; q < nops; q = nops) out[q] = (uint32_t)isid[op_item[q]];
-}
-__global__ __launch_bounds__(kBlock) void k_xw_heads_u32(const uint32_t* k, int64_t n, uint32_t* head) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n)
-    head[i] = (i == 0 || k[i] != k[i - 1]) ? 1u : 0u;
-}
-__global__ __launch_bounds__(kBlock) void k_xw_head_list(const uint32_t* head, const uint32_t* hoff, int64_t n,
-                                                         uint32_t* hl) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n)
-    if (head[i]) hl[hoff[i]] = (uint32_t)i;
-}
-__global__ __launch_bounds__(kBlock) void k_xw_fill_u64(uint64_t* p, int64_t n, uint64_t v) {
-  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) p[i] = v;
 }
 
 // ---------------------------------------------------------------- batch windows
@@ -941,13 +887,7 @@ __global__ __launch_bounds__(kBlock) void k_xb_added(int64_t total, int64_t C, c
 
 // carried items of the segment [s, s + ck) already added: a prefix (FIFO)
 __device__ __forceinline__ int64_t xb_added_count(const uint8_t* added_j, int64_t s, int64_t ck) {
-  int64_t lo = s, hi = s + ck;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (added_j[mid]) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo - s;
+  return first_false(s, s + ck, [=](int64_t i) { return added_j[i] != 0; }) - s;
 }
 
 struct XbArgs {
@@ -1167,12 +1107,7 @@ __global__ __launch_bounds__(kBlock) void k_xb_ops(const XbOpArgs* __restrict__ 
     const uint32_t it = a.sp[j];
     const uint64_t ao = a.aopp[j], eo = a.eopp[j];
     if (ao != kNoOpp) {
-      int64_t lo = s, hi = e;   // expirations at or before this flush
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.eopp[mid] <= ao) lo = mid + 1;
-        else hi = mid;
-      }
+      const int64_t lo = upper_bound(a.eopp, s, e, ao);   // expirations at or before this flush
       const int64_t q = base + (j - s - na) + (lo - s);
       const uint32_t f = (uint32_t)(ao >> 1);
       a.op_item[q] = it;
@@ -1184,12 +1119,7 @@ __global__ __launch_bounds__(kBlock) void k_xb_ops(const XbOpArgs* __restrict__ 
       a.op_epoch[q] = a.epoch_j[j];
     }
     if (eo != kNoOpp) {
-      int64_t lo = s + na, hi = e;   // adds at earlier flushes
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (a.aopp[mid] < eo) lo = mid + 1;
-        else hi = mid;
-      }
+      const int64_t lo = lower_bound(a.aopp, s + na, e, eo);   // adds at earlier flushes
       const int64_t q = base + (j - s) + (lo - s - na);
       const uint32_t f = (uint32_t)(eo >> 1);
       a.op_item[q] = it;
@@ -1502,6 +1432,37 @@ struct WindowTotalsHost : WindowTotals {
   int64_t last_out;   // copy of the last output sequence (last_out)
 };
 
+// Both slots of the window items (double-buffered: a push reads slot `cur`
+// and carries into the other).  Every column operation walks kItemCol.
+struct ItemStore {
+  int nsub[kItemSubs] = {1, 0, 0};   // sub-columns per ItemSub: 1, ncols, nagg
+  int cur = 0;
+  int64_t cap[2] = {0, 0};
+  DevBuf buf[2][kItemCols];
+
+  void alloc(int s, int64_t n) {
+    for (int c = 0; c < kItemCols; c++)
+      buf[s][c].reserve((size_t)std::max(nsub[kItemCol[c].sub], 1) * n * kItemCol[c].size);
+    cap[s] = n;
+  }
+  ItemPtrs ptrs(int s) const {
+    void* v[kItemCols];
+    for (int c = 0; c < kItemCols; c++) v[c] = buf[s][c].p;
+    ItemPtrs p;
+    std::memcpy(&p, v, sizeof(p));
+    return p;
+  }
+  char* at(int s, int c, int sub) const { return buf[s][c].as<char>() + (size_t)sub * cap[s] * kItemCol[c].size; }
+  // f(column, sub-column) for every sub-column, in snapshot order: the
+  // per-item columns, then each attribute's columns, then each aggregator's
+  template <class F> void each(F f) const {
+    for (int k = 0; k < kItemSubs; k++)
+      for (int sub = 0; sub < nsub[k]; sub++)
+        for (int c = 0; c < kItemCols; c++)
+          if (kItemCol[c].sub == k) f(c, sub);
+  }
+};
+
 struct WindowXEngine : Engine {
   std::vector<int> filters;
   int wkind = 0;
@@ -1513,11 +1474,9 @@ struct WindowXEngine : Engine {
   int nagg = 0, ncols = 0, nw = 0;
   bool group = false, plain = false;
   GroupDict gd;
-  // window items, double-buffered: [0, C) carried (key-sorted, FIFO inside a key)
+  // window items: [0, C) of slot items.cur carried (key-sorted, FIFO inside a key)
   int64_t C = 0;
-  int cur = 0;
-  int64_t icap[2] = {0, 0};
-  DevBuf ipk[2], its[2], iseq[2], isid[2], ilast[2], icall[2], irow[2], iattr[2], inul[2], iargv[2], iargn[2];
+  ItemStore items;
   // pending notify entries (time windows with timers): grouped by key (sorted),
   // each key's entries in queue (FIFO) order
   int64_t np = 0;
@@ -1534,8 +1493,6 @@ struct WindowXEngine : Engine {
   int64_t tb_next = -1;
   std::deque<int64_t> tb_notify;
   int bmode = 0;   // XB_* (k_xb_opp)
-  DevBuf xb_added, xb_aopp, xb_trig, xb_fr, xb_fnow, xb_fseq, xb_bflush, xb_ccount, xb_clast, xb_epoch, xb_keep,
-      xb_last, xb_cchunk, xb_cflush, xb_cepoch, op_epoch;
   int64_t tb_epoch = -1;   // stream.current.event timeBatch: global chunk id of the last flush
   // externalTimeBatch: the packed parameters (siddhi_ir.h); each key's
   // (startTime, endTime, lastCurrentEventTime) is carried as three entries of
@@ -1543,14 +1500,33 @@ struct WindowXEngine : Engine {
   // has a segment in every push and the list is rewritten in segment order)
   int etb_ts_col = 0, etb_start_mode = 0, etb_start_col = 0, etb_replace = 0;
   int64_t etb_start_const = 0;
+
+  // ---- per-push scratch, by the phase that first writes it
+  // calls and clock
+  DevBuf d_offs, d_call_of, d_last, d_call_now, d_F, d_fnow;
+  // filter, partition key, runs
+  DevBuf d_flags, d_cnt, d_off, d_pkey, d_start, d_run;
+  // new items: their state key words
+  DevBuf kw, kn, kh;
+  // key segments
+  DevBuf spk, spk2, sp, sp2, head, hscan, segS, segid, segCk, pA, pB, proom;
+  // sliding windows: expiry, timer order
+  DevBuf proom_off, etid, rec, tF, tHead, tSeg, ntimer, pout_pk, pout_v, pcnt, pcnt_off, last_out, tperm, tperm2, tk32,
+      tk32b, tk64, tk64b, trank, sF, d_runs_before;
+  // batch windows: flushes, opportunities
+  DevBuf xb_added, xb_aopp, xb_trig, xb_fr, xb_fnow, xb_fseq, xb_bflush, xb_ccount, xb_clast, xb_epoch, xb_keep,
+      xb_last, xb_cchunk, xb_cflush, xb_cepoch, op_epoch;
   DevBuf etb_M, etb_head, etb_E, etb_trigj, etb_tjx, etb_tpos, etb_tv, etb_tf, etb_seg_start, etb_seg_end, etb_seg_j1;
-  // per-push scratch
-  DevBuf d_offs, d_call_of, d_last, d_call_now, d_F, d_fnow, d_flags, d_cnt, d_off, d_pkey, d_start,
-      d_run, d_runs_before, d_scan, d_sort, kw, kn, kh, spk, spk2, sp, sp2, head, hscan, segS, segid, segCk,
-      pA, pB, proom, proom_off, eopp, etid, rec, tF, tHead, tSeg, ntimer, pout_pk, pout_v, pcnt, pcnt_off, last_out,
-      seg_pk, okeep, okoff, tperm, tperm2, tk32, tk32b, tk64, tk64b, trank, sF, nops_b, opscan, op_item, op_add, op_on,
-      op_chunk, op_now, op_seq, osid, osid2, oq, oq2, ohead, ohoff, ohl, resv, resn, rowflag, rowsrc, roff, rkey, rkey2,
-      rq, rq2, keep, koff, pend_tmp_pk, pend_tmp_v, pend_idx, pend_idx2, pend_key2;
+  // operations (either kind of window)
+  DevBuf eopp, nops_b, opscan, op_item, op_add, op_on, op_chunk, op_now, op_seq;
+  // fold and row selection
+  DevBuf osid, osid2, oq, oq2, ohead, ohoff, ohl, resv, resn, rowflag, rowsrc, roff;
+  // emit
+  DevBuf rkey, rkey2, rq, rq2;
+  // carry and pending
+  DevBuf keep, koff, seg_pk, okeep, okoff, pend_tmp_pk, pend_tmp_v, pend_idx, pend_idx2, pend_key2;
+  // scan and sort work space
+  DevBuf d_scan, d_sort;
   PinnedBuf h_last, h_pin;
   ReadbackBlock<WindowTotals, WindowTotalsHost> tot;
   std::vector<int64_t> h_offs, h_now;
@@ -1591,85 +1567,40 @@ struct WindowXEngine : Engine {
   }
 
   // ---- storage
-  void alloc_slot(int s, int64_t cap) {
-    const int64_t nc = std::max(ncols, 1), na = std::max(nagg, 1);
-    ipk[s].reserve(cap * 8);
-    its[s].reserve(cap * 8);
-    iseq[s].reserve(cap * 8);
-    isid[s].reserve(cap * 8);
-    ilast[s].reserve(cap * 8);
-    icall[s].reserve(cap * 4);
-    irow[s].reserve(cap * 4);
-    iattr[s].reserve(nc * cap * 8);
-    inul[s].reserve(nc * cap);
-    iargv[s].reserve(na * cap * 8);
-    iargn[s].reserve(na * cap);
-    icap[s] = cap;
-  }
-  // slot `cur` with room for `need` items, its [0, C) preserved
+  // slot items.cur with room for `need` items, its [0, C) preserved
   void ensure_items(int64_t need) {
-    if (icap[cur] >= need) return;
-    const int nw_ = cur ^ 1;
-    const int64_t cap = std::max<int64_t>(need, std::max<int64_t>(1024, icap[cur] * 2));
-    alloc_slot(nw_, cap);
-    hipStream_t s = stream;
-    if (C > 0) {
-      SHD_HIP(hipMemcpyAsync(ipk[nw_].p, ipk[cur].p, C * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(its[nw_].p, its[cur].p, C * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(iseq[nw_].p, iseq[cur].p, C * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(isid[nw_].p, isid[cur].p, C * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(ilast[nw_].p, ilast[cur].p, C * 8, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(icall[nw_].p, icall[cur].p, C * 4, hipMemcpyDeviceToDevice, s));
-      SHD_HIP(hipMemcpyAsync(irow[nw_].p, irow[cur].p, C * 4, hipMemcpyDeviceToDevice, s));
-      for (int c = 0; c < ncols; c++) {
-        SHD_HIP(hipMemcpyAsync(iattr[nw_].as<uint64_t>() + c * cap, iattr[cur].as<uint64_t>() + c * icap[cur], C * 8,
-                               hipMemcpyDeviceToDevice, s));
-        SHD_HIP(hipMemcpyAsync(inul[nw_].as<uint8_t>() + c * cap, inul[cur].as<uint8_t>() + c * icap[cur], C,
-                               hipMemcpyDeviceToDevice, s));
-      }
-      for (int g = 0; g < nagg; g++) {
-        SHD_HIP(hipMemcpyAsync(iargv[nw_].as<uint64_t>() + g * cap, iargv[cur].as<uint64_t>() + g * icap[cur], C * 8,
-                               hipMemcpyDeviceToDevice, s));
-        SHD_HIP(hipMemcpyAsync(iargn[nw_].as<uint8_t>() + g * cap, iargn[cur].as<uint8_t>() + g * icap[cur], C,
-                               hipMemcpyDeviceToDevice, s));
-      }
-    }
-    cur = nw_;
+    const int from = items.cur, to = from ^ 1;
+    if (items.cap[from] >= need) return;
+    items.alloc(to, std::max<int64_t>(need, std::max<int64_t>(1024, items.cap[from] * 2)));
+    if (C > 0)
+      items.each([&](int c, int sub) {
+        SHD_HIP(hipMemcpyAsync(items.at(to, c, sub), items.at(from, c, sub), C * kItemCol[c].size,
+                               hipMemcpyDeviceToDevice, stream));
+      });
+    items.cur = to;
+  }
+  // A [rows][n] table of 8-byte cells becomes [rows][n2]: new cells are filled
+  // with `fill` bytes, the old rows copied.
+  void grow_table(DevBuf& t, int rows, int64_t n, int64_t n2, int fill) {
+    DevBuf g;
+    g.reserve((size_t)rows * n2 * 8);
+    SHD_HIP(hipMemsetAsync(g.p, fill, (size_t)rows * n2 * 8, stream));
+    for (int r = 0; r < rows && n; r++)
+      SHD_HIP(hipMemcpyAsync(g.as<int64_t>() + r * n2, t.as<int64_t>() + r * n, n * 8, hipMemcpyDeviceToDevice, stream));
+    SHD_HIP(hipStreamSynchronize(stream));
+    t.swap(g);
+  }
+  // the aggregator state tables with exactly ns states per row
+  void grow_states(int64_t ns) {
+    grow_table(g_dsum, nagg, nstates, ns, 0);
+    grow_table(g_lsum, nagg, nstates, ns, 0);
+    grow_table(g_cnt, nagg, nstates, ns, 0);
+    if (batch) grow_table(g_epoch, 1, nstates, ns, 0xFF);
+    nstates = ns;
   }
   void ensure_states(int64_t n) {
-    if (n <= nstates || nagg == 0) {
-      if (nagg == 0) nstates = std::max(nstates, n);
-      return;
-    }
-    const int64_t ns = std::max<int64_t>(n, std::max<int64_t>(1024, nstates * 2));
-    DevBuf a, l, c;
-    a.reserve((size_t)nagg * ns * 8);
-    l.reserve((size_t)nagg * ns * 8);
-    c.reserve((size_t)nagg * ns * 8);
-    SHD_HIP(hipMemsetAsync(a.p, 0, (size_t)nagg * ns * 8, stream));
-    SHD_HIP(hipMemsetAsync(l.p, 0, (size_t)nagg * ns * 8, stream));
-    SHD_HIP(hipMemsetAsync(c.p, 0, (size_t)nagg * ns * 8, stream));
-    for (int g = 0; g < nagg && nstates; g++) {
-      SHD_HIP(hipMemcpyAsync(a.as<double>() + g * ns, g_dsum.as<double>() + g * nstates, nstates * 8,
-                             hipMemcpyDeviceToDevice, stream));
-      SHD_HIP(hipMemcpyAsync(l.as<int64_t>() + g * ns, g_lsum.as<int64_t>() + g * nstates, nstates * 8,
-                             hipMemcpyDeviceToDevice, stream));
-      SHD_HIP(hipMemcpyAsync(c.as<int64_t>() + g * ns, g_cnt.as<int64_t>() + g * nstates, nstates * 8,
-                             hipMemcpyDeviceToDevice, stream));
-    }
-    SHD_HIP(hipStreamSynchronize(stream));
-    if (batch) {
-      DevBuf ep;
-      ep.reserve((size_t)ns * 8);
-      SHD_HIP(hipMemsetAsync(ep.p, 0xFF, (size_t)ns * 8, stream));
-      if (nstates) SHD_HIP(hipMemcpyAsync(ep.p, g_epoch.p, nstates * 8, hipMemcpyDeviceToDevice, stream));
-      SHD_HIP(hipStreamSynchronize(stream));
-      std::swap(g_epoch.p, ep.p); std::swap(g_epoch.cap, ep.cap);
-    }
-    std::swap(g_dsum.p, a.p); std::swap(g_dsum.cap, a.cap);
-    std::swap(g_lsum.p, l.p); std::swap(g_lsum.cap, l.cap);
-    std::swap(g_cnt.p, c.p); std::swap(g_cnt.cap, c.cap);
-    nstates = ns;
+    if (nagg == 0) nstates = std::max(nstates, n);
+    else if (n > nstates) grow_states(std::max<int64_t>(n, std::max<int64_t>(1024, nstates * 2)));
   }
 
   template <class T> void upload(DevBuf& d, const std::vector<T>& v) {
@@ -1686,10 +1617,52 @@ struct WindowXEngine : Engine {
     tot.reserve();
     return Engine::scan(in, outp, n, &tot.dev()->scan_total, &tot.host().scan_total, d_scan);
   }
+  // stable sort of (key, value) pairs; returns the values' final array
+  const uint32_t* sort_u32(DevBuf& k, DevBuf& v, DevBuf& k2, DevBuf& v2, int64_t n, int bits, const uint32_t** keys) {
+    bool alt = false;
+    radix_sort_pairs_u32(k.as<uint32_t>(), v.as<uint32_t>(), k2.as<uint32_t>(), v2.as<uint32_t>(), n, bits, d_sort,
+                         stream, alt);
+    if (keys) *keys = (alt ? k2 : k).as<uint32_t>();
+    return (alt ? v2 : v).as<uint32_t>();
+  }
+  const uint32_t* sort_u64(DevBuf& k, DevBuf& v, DevBuf& k2, DevBuf& v2, int64_t n, int bits, const uint64_t** keys) {
+    bool alt = false;
+    radix_sort_pairs_u64(k.as<uint64_t>(), v.as<uint32_t>(), k2.as<uint64_t>(), v2.as<uint32_t>(), n, bits, d_sort,
+                         stream, alt);
+    if (keys) *keys = (alt ? k2 : k).as<uint64_t>();
+    return (alt ? v2 : v).as<uint32_t>();
+  }
 
   // ---- push
-  // ncalls InputHandler calls over n events; clock moves per call when `advance`;
-  // `extra_move`: one clock move to `extra_t` with no events (shd_set_time).
+  // The scalars of one push, filled in phase by phase.
+  struct Push {
+    const Staged& b;
+    bool extra_move;      // one clock move to `extra_t` with no events (shd_set_time)
+    int64_t extra_t;
+    int64_t n;            // events
+    int ncalls = 0;       // InputHandler calls over them
+    std::vector<char> moved;   // per call: the clock moved
+    int64_t clk = 0;      // the clock after the push
+    bool timers = false;  // the window runs TIMER chunks
+    int nf = 0;           // clock moves they see
+    XwArgs xa{};
+    int64_t m = 0;        // new items
+    uint32_t nruns = 0;   // partition runs
+    int64_t total = 0;    // carried + new items
+    int64_t cap = 0;      // capacity of the item slot in use
+    ItemPtrs it{};        // its columns
+    int64_t nseg = 0;     // key segments
+    const uint32_t* SP = nullptr;   // the items in (key, FIFO) order
+    int64_t nt = 0;       // TIMER chunks
+    bool lane_ran = false;
+    int64_t nflush = 0;   // batch windows: output chunks
+    int64_t nops = 0, nrows = 0;
+  };
+  // output chunks of the push
+  int64_t chunks(const Push& P) const {
+    return batch ? P.nflush : P.nt + (partitioned ? (int64_t)P.nruns : (int64_t)P.ncalls);
+  }
+
   void push(const Staged& b) override { run(b, false, 0); }
 
   void set_time(int64_t t) override {
@@ -1708,68 +1681,94 @@ struct WindowXEngine : Engine {
   }
 
   void run(const Staged& b, bool extra_move, int64_t extra_t) {
-    hipStream_t s = stream;
-    const int64_t n = b.n;
-    SHD_HIP(hipEventRecord(ev0, s));
+    Push P{b, extra_move, extra_t, b.n};
+    SHD_HIP(hipEventRecord(ev0, stream));
     stage_begin();
-    // ---- calls and clock moves (TimestampGeneratorImpl.setCurrentTimestamp per call, playback)
-    h_offs = b.call_offsets;
+    push_calls(P);
+    push_filter(P);
+    mark("filter");
+    push_items(P);
+    mark("window_items");
+    push_segments(P);
+    mark("segments");
+    if (batch) {
+      batch_operations(P);
+    } else {
+      expiry(P);
+      mark("expiry");
+      timer_order(P);
+      sliding_operations(P);
+    }
+    mark("operations");
+    push_fold(P);   // marks "fold" when the push has operations
+    push_emit(P);
+    mark("emit");
+    push_carry(P);
+    mark("carry");
+    push_counters(P);
+  }
+
+  // calls and clock moves (TimestampGeneratorImpl.setCurrentTimestamp per call, playback)
+  void push_calls(Push& P) {
+    const int64_t n = P.n;
+    h_offs = P.b.call_offsets;
     if (h_offs.size() < 2) h_offs = {0, n};
-    const int ncalls = (int)h_offs.size() - 1;
+    const int ncalls = P.ncalls = (int)h_offs.size() - 1;
     upload(d_offs, h_offs);
     d_call_of.reserve(std::max<int64_t>(n, 1) * 4);
     d_last.reserve((size_t)ncalls * 8);
-    if (n > 0) {
-      hipLaunchKernelGGL(k_xw_calls, dim3((unsigned)ncalls), dim3(kBlock), 0, s, (const int64_t*)d_offs.as<int64_t>(),
-                         ncalls, b.cs.ts, d_call_of.as<int32_t>(), d_last.as<int64_t>());
-      SHD_CHECK_LAUNCH();
-    }
     std::vector<int64_t> last(ncalls, INT64_MIN);
     if (n > 0) {
+      launch_grid(k_call_of, (unsigned)ncalls, d_offs.as<int64_t>(), ncalls, P.b.cs.ts, d_call_of.as<int32_t>(),
+                  d_last.as<int64_t>());
       h_last.reserve((size_t)ncalls * 8);
-      SHD_HIP(hipMemcpyAsync(h_last.p, d_last.p, (size_t)ncalls * 8, hipMemcpyDeviceToHost, s));
-      SHD_HIP(hipStreamSynchronize(s));
+      SHD_HIP(hipMemcpyAsync(h_last.p, d_last.p, (size_t)ncalls * 8, hipMemcpyDeviceToHost, stream));
+      SHD_HIP(hipStreamSynchronize(stream));
       std::memcpy(last.data(), h_last.p, (size_t)ncalls * 8);
     }
     h_now.assign(ncalls, now);
     h_F.clear();
     h_fnow.clear();
-    int64_t clk = now;
-    std::vector<char> moved(ncalls, 0);
+    P.clk = now;
+    P.moved.assign(ncalls, 0);
     for (int c = 0; c < ncalls; c++) {
       int64_t t = INT64_MIN;
       bool move = false;
-      if (extra_move && c == 0) {
-        t = extra_t;
+      if (P.extra_move && c == 0) {
+        t = P.extra_t;
         move = true;
-      } else if (b.advance_time && h_offs[c + 1] > h_offs[c]) {
+      } else if (P.b.advance_time && h_offs[c + 1] > h_offs[c]) {
         t = last[c];
         move = true;   // InputHandler.send(Event[]) with events
       }
-      if (move && t >= clk) {
-        clk = t;
+      if (move && t >= P.clk) {
+        P.clk = t;
         h_F.push_back(c);
         h_fnow.push_back(t);
-        moved[c] = 1;
+        P.moved[c] = 1;
       }
-      h_now[c] = clk;
+      h_now[c] = P.clk;
     }
-    const bool timers = timed() && plan.expired_on;
-    if (!timers) {   // clock moves only matter to the TIMER chunks
+    P.timers = timed() && plan.expired_on;
+    if (!P.timers) {   // clock moves only matter to the TIMER chunks
       h_F.clear();
       h_fnow.clear();
     }
     upload(d_call_now, h_now);
     upload(d_F, h_F);
     upload(d_fnow, h_fnow);
-    const int nf = (int)h_F.size();
-    // ---- filter, partition key, runs
+    P.nf = (int)h_F.size();
+  }
+
+  // filter, partition key, partition runs
+  void push_filter(Push& P) {
+    const int64_t n = P.n;
     d_flags.reserve(std::max<int64_t>(n, 1));
     d_cnt.reserve(std::max<int64_t>(n, 1) * 4);
     d_off.reserve(std::max<int64_t>(n, 1) * 4);
     d_pkey.reserve(std::max<int64_t>(n, 1) * 8);
-    XwArgs xa{};
-    xa.cs = b.cs;
+    XwArgs& xa = P.xa;
+    xa.cs = P.b.cs;
     xa.es = dset();
     xa.filters = dfilters(filters);
     xa.partitioned = partitioned;
@@ -1794,128 +1793,102 @@ struct WindowXEngine : Engine {
     xa.nw = nw;
     xa.C = C;
     xa.seq0 = seq;
-    int64_t m = 0;
-    uint32_t nruns = 0;
-    const XwArgs* d_xa = nullptr;
-    if (n > 0) {
-      d_xa = dev_args(xa);
-      hipLaunchKernelGGL(k_xw_filter, dim3(grid_cover(n)), dim3(kBlock), 0, s, d_xa, n, d_flags.as<uint8_t>(),
-                         d_cnt.as<uint32_t>(), d_pkey.as<uint64_t>());
-      SHD_CHECK_LAUNCH();
-      m = scan(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n);
-      if (partitioned) {
-        d_start.reserve(n * 4);
-        d_run.reserve(n * 4);
-        hipLaunchKernelGGL(k_xw_run_starts, dim3(grid_cover(n)), dim3(kBlock), 0, s, (const uint8_t*)d_flags.as<uint8_t>(),
-                           (const uint64_t*)d_pkey.as<uint64_t>(), (const int32_t*)d_call_of.as<int32_t>(), n,
-                           d_start.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-        nruns = scan(d_start.as<uint32_t>(), d_run.as<uint32_t>(), n);
-        // run id of event i = exclusive count + own start - 1: k_xw_ops reads the
-        // exclusive count at a run's events; fix it up to the inclusive id
-      }
+    if (n <= 0) return;
+    launch(k_xw_filter, n, dev_args(xa), n, d_flags.as<uint8_t>(), d_cnt.as<uint32_t>(), d_pkey.as<uint64_t>());
+    P.m = scan(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n);
+    if (partitioned) {
+      d_start.reserve(n * 4);
+      d_run.reserve(n * 4);
+      launch(k_run_starts, n, d_flags.as<uint8_t>(), d_pkey.as<uint64_t>(), d_call_of.as<int32_t>(), n,
+             d_start.as<uint32_t>());
+      // d_run: the exclusive count of run starts; run_ids() makes the inclusive ids of it
+      P.nruns = scan(d_start.as<uint32_t>(), d_run.as<uint32_t>(), n);
     }
-    mark("filter");
-    const int64_t total = C + m;
-    if (total >= (int64_t)INT32_MAX) throw Error(SHD_E_CAPACITY, "window items exceed 2^31");
-    // ---- new items
-    ensure_items(std::max<int64_t>(total, 1));
-    const int64_t cap = icap[cur];
-    xa.cap = cap;
+  }
+
+  // new items [C, C + m) and their state ids
+  void push_items(Push& P) {
+    const int64_t n = P.n, m = P.m;
+    P.total = C + m;
+    if (P.total >= (int64_t)INT32_MAX) throw Error(SHD_E_CAPACITY, "window items exceed 2^31");
+    ensure_items(std::max<int64_t>(P.total, 1));
+    P.cap = P.xa.cap = items.cap[items.cur];
+    P.it = items.ptrs(items.cur);
     if (m > 0) {
       kw.reserve((size_t)std::max(nw, 1) * m * 8);
       kn.reserve(m);
       kh.reserve(m * 8);
-      ItemOut io{ipk[cur].as<uint64_t>(), its[cur].as<int64_t>(), iseq[cur].as<int64_t>(), icall[cur].as<int32_t>(),
-                 irow[cur].as<int32_t>(), iattr[cur].as<uint64_t>(), inul[cur].as<uint8_t>(),
-                 iargv[cur].as<uint64_t>(), iargn[cur].as<uint8_t>(), kw.as<uint64_t>(), kn.as<uint8_t>(),
-                 kh.as<uint64_t>()};
-      d_xa = dev_args(xa);
-      hipLaunchKernelGGL(k_xw_items, dim3(grid_cover(n)), dim3(kBlock), 0, s, d_xa, dev_args(io), n,
-                         (const uint32_t*)d_cnt.as<uint32_t>(), (const uint32_t*)d_off.as<uint32_t>(),
-                         (const uint64_t*)d_pkey.as<uint64_t>(), (const int32_t*)d_call_of.as<int32_t>(), m);
-      SHD_CHECK_LAUNCH();
+      const ItemOut io{P.it, kw.as<uint64_t>(), kn.as<uint8_t>(), kh.as<uint64_t>()};
+      const XwArgs* d_xa = dev_args(P.xa);
+      launch(k_xw_items, n, d_xa, dev_args(io), n, d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), d_pkey.as<uint64_t>(),
+             d_call_of.as<int32_t>(), m);
       if (nw > 0) {
         gd.nk = nw;
-        gd.assign(m, kh.as<uint64_t>(), kw.as<uint64_t>(), kn.as<uint8_t>(), m, isid[cur].as<uint64_t>(), C, s);
+        gd.assign(m, kh.as<uint64_t>(), kw.as<uint64_t>(), kn.as<uint8_t>(), m, P.it.sid, C, stream);
       } else {
-        hipLaunchKernelGGL(k_xw_fill_u64, dim3(grid_cover(m)), dim3(kBlock), 0, s, isid[cur].as<uint64_t>() + C, m,
-                           (uint64_t)0);
-        SHD_CHECK_LAUNCH();
+        launch(k_fill_u64, m, P.it.sid + C, m, 0);
       }
     }
     ensure_states(nw > 0 ? std::max<int64_t>(gd.count, 1) : 1);
-    mark("window_items");
-    // ---- key segments: stable sort by partition key (carried first, FIFO kept)
+  }
+
+  // key segments: stable sort by partition key (carried first, FIFO kept)
+  void push_segments(Push& P) {
+    hipStream_t s = stream;
+    const int64_t total = P.total;
     sp.reserve(std::max<int64_t>(total, 1) * 4);
-    int64_t nseg = 0;
     if (total > 0) {
       fill_iota_u32(sp.as<uint32_t>(), total, 0, s);
       spk.reserve(total * 8);
-      SHD_HIP(hipMemcpyAsync(spk.p, ipk[cur].p, total * 8, hipMemcpyDeviceToDevice, s));
+      SHD_HIP(hipMemcpyAsync(spk.p, P.it.pk, total * 8, hipMemcpyDeviceToDevice, s));
       const uint32_t* spv = sp.as<uint32_t>();
       const uint64_t* spkv = spk.as<uint64_t>();
       if (partitioned) {
         tot.reserve();
-        reduce_max_u64(ipk[cur].as<uint64_t>(), total, &tot.dev()->kmax, s);
+        reduce_max_u64(P.it.pk, total, &tot.dev()->kmax, s);
         tot.fetch(&WindowTotals::kmax, s);
         SHD_HIP(hipStreamSynchronize(s));
-        const uint64_t kmax = tot.host().kmax;
         spk2.reserve(total * 8);
         sp2.reserve(total * 4);
-        bool alt = false;
-        radix_sort_pairs_u64(spk.as<uint64_t>(), sp.as<uint32_t>(), spk2.as<uint64_t>(), sp2.as<uint32_t>(), total,
-                             bits_for(kmax), d_sort, s, alt);
-        spv = alt ? sp2.as<uint32_t>() : sp.as<uint32_t>();
-        spkv = alt ? spk2.as<uint64_t>() : spk.as<uint64_t>();
+        spv = sort_u64(spk, sp, spk2, sp2, total, bits_for(tot.host().kmax), &spkv);
       }
       head.reserve(total * 4);
       hscan.reserve(total * 4);
-      hipLaunchKernelGGL(k_xw_seg_heads, dim3(grid_cover(total)), dim3(kBlock), 0, s, spkv, total, head.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-      nseg = scan(head.as<uint32_t>(), hscan.as<uint32_t>(), total);
-      segS.reserve((nseg + 1) * 8);
+      launch(k_seg_heads_u64, total, spkv, total, head.as<uint32_t>());
+      P.nseg = scan(head.as<uint32_t>(), hscan.as<uint32_t>(), total);
+      segS.reserve((P.nseg + 1) * 8);
       segid.reserve(total * 4);
-      hipLaunchKernelGGL(k_xw_seg_list, dim3(grid_cover(total)), dim3(kBlock), 0, s, (const uint32_t*)head.as<uint32_t>(),
-                         (const uint32_t*)hscan.as<uint32_t>(), total, segS.as<int64_t>(), segid.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
+      launch(k_xw_seg_list, total, head.as<uint32_t>(), hscan.as<uint32_t>(), total, segS.as<int64_t>(),
+             segid.as<uint32_t>());
       if (spv != sp.as<uint32_t>()) SHD_HIP(hipMemcpyAsync(sp.p, spv, total * 4, hipMemcpyDeviceToDevice, s));
     }
-    const uint32_t* SP = sp.as<uint32_t>();
+    P.SP = sp.as<uint32_t>();
+    const int64_t nseg = P.nseg;
     segCk.reserve((nseg + 1) * 8);
     pA.reserve((nseg + 1) * 8);
     pB.reserve((nseg + 1) * 8);
     proom.reserve((nseg + 1) * 4);
     proom_off.reserve((nseg + 1) * 4);
-    if (nseg > 0) {
-      hipLaunchKernelGGL(k_xw_seg_info, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, nseg,
-                         (const int64_t*)segS.as<int64_t>(), SP, C, (const uint64_t*)ipk[cur].as<uint64_t>(),
-                         (const uint64_t*)ppk.as<uint64_t>(), np, segCk.as<int64_t>(), pA.as<int64_t>(),
-                         pB.as<int64_t>(), proom.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-    }
-    mark("segments");
-    int64_t nt = 0, nflush = 0, nops = 0;
-    bool lane_ran = false;
-    if (batch) {
-      // ---- batch windows: flushes, opportunities, operations
-      nops = batch_operations(n, m, total, ncalls, nseg, moved, SP, nflush);
-      mark("operations");
-    } else {
-    // ---- expiry opportunities
+    if (nseg > 0)
+      launch(k_xw_seg_info, nseg, nseg, segS.as<int64_t>(), P.SP, C, P.it.pk, ppk.as<uint64_t>(), np,
+             segCk.as<int64_t>(), pA.as<int64_t>(), pB.as<int64_t>(), proom.as<uint32_t>());
+  }
+
+  // sliding windows: each item's expiry opportunity
+  void expiry(Push& P) {
+    hipStream_t s = stream;
+    const int64_t total = P.total, nseg = P.nseg;
     eopp.reserve(std::max<int64_t>(total, 1) * 8);
     etid.reserve(std::max<int64_t>(total, 1) * 4);
     if (total > 0 && wkind == SHD_W_LENGTH) {
-      hipLaunchKernelGGL(k_xw_len_expiry, dim3(grid_cover(total)), dim3(kBlock), 0, s, total, wparam,
-                         (const int64_t*)segS.as<int64_t>(), (const uint32_t*)segid.as<uint32_t>(), SP,
-                         (const int32_t*)irow[cur].as<int32_t>(), eopp.as<uint64_t>(), etid.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
+      launch(k_xw_len_expiry, total, total, wparam, segS.as<int64_t>(), segid.as<uint32_t>(), P.SP, P.it.row,
+             eopp.as<uint64_t>(), etid.as<uint32_t>());
     } else if (total > 0 && time_like()) {
       const uint32_t room = nseg > 0 ? scan(proom.as<uint32_t>(), proom_off.as<uint32_t>(), nseg) : 0;
       rec.reserve(total);
-      tF.reserve((np + m + 1) * 4);
-      tHead.reserve((np + m + 1) * 8);
-      tSeg.reserve((np + m + 1) * 4);
+      tF.reserve((np + P.m + 1) * 4);
+      tHead.reserve((np + P.m + 1) * 8);
+      tSeg.reserve((np + P.m + 1) * 4);
       ntimer.reserve(64);
       pout_pk.reserve(std::max<uint32_t>(room, 1) * 8);
       pout_v.reserve(std::max<uint32_t>(room, 1) * 8);
@@ -1930,22 +1903,22 @@ struct WindowXEngine : Engine {
       la.pA = pA.as<int64_t>();
       la.pB = pB.as<int64_t>();
       la.proom_off = proom_off.as<uint32_t>();
-      la.sp = SP;
-      la.ipk = ipk[cur].as<uint64_t>();
-      la.its = its[cur].as<int64_t>();
-      la.icall = icall[cur].as<int32_t>();
-      la.irow = irow[cur].as<int32_t>();
-      la.ilast = ilast[cur].as<int64_t>();
+      la.sp = P.SP;
+      la.ipk = P.it.pk;
+      la.its = P.it.ts;
+      la.icall = P.it.call;
+      la.irow = P.it.row;
+      la.ilast = P.it.last;
       la.call_now = d_call_now.as<int64_t>();
       la.offs = d_offs.as<int64_t>();
       la.F = d_F.as<int32_t>();
       la.fnow = d_fnow.as<int64_t>();
-      la.nf = nf;
+      la.nf = P.nf;
       la.T = wparam;
       la.L = wkind == SHD_W_TIME_LENGTH ? wparam2 : 0;
       la.ext_col = wkind == SHD_W_EXTERNAL_TIME ? (int)wparam2 : -1;
-      la.iattr = iattr[cur].as<uint64_t>();
-      la.cap = cap;
+      la.iattr = P.it.attr;
+      la.cap = P.cap;
       la.partitioned = partitioned;
       la.last_global = last_global;
       la.pv = pv.as<int64_t>();
@@ -1960,308 +1933,102 @@ struct WindowXEngine : Engine {
       la.pout_v = pout_v.as<int64_t>();
       la.pcnt = pcnt.as<uint32_t>();
       la.last_out = last_out.as<int64_t>();
-      hipLaunchKernelGGL(k_xw_time_lane, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, dev_args(la));
-      SHD_CHECK_LAUNCH();
+      launch(k_xw_time_lane, nseg, dev_args(la));
       tot.reserve();
-      nt = read_u32(ntimer.p, &tot.host().n_timer);
-      lane_ran = true;
+      P.nt = read_u32(ntimer.p, &tot.host().n_timer);
+      P.lane_ran = true;
     } else if (total > 0) {   // no window: items never expire
-      hipLaunchKernelGGL(k_xw_fill_u64, dim3(grid_cover(total)), dim3(kBlock), 0, s, eopp.as<uint64_t>(), total, kNoOpp);
-      SHD_CHECK_LAUNCH();
+      launch(k_fill_u64, total, eopp.as<uint64_t>(), total, kNoOpp);
       SHD_HIP(hipMemsetAsync(etid.p, 0xFF, total * 4, s));
     }
-    mark("expiry");
-    // ---- timers in (call, notify head, key) order: the TIMER chunks' order
-    //      (Scheduler.onTimeChange: sortedExpires by time; ties by key order)
+  }
+
+  // timers in (call, notify head, key) order: the TIMER chunks' order
+  // (Scheduler.onTimeChange: sortedExpires by time; ties by key order)
+  void timer_order(Push& P) {
+    hipStream_t s = stream;
+    const int64_t nt = P.nt;
     trank.reserve(std::max<int64_t>(nt, 1) * 4);
     sF.reserve(std::max<int64_t>(nt, 1) * 4);
-    if (nt > 0) {
-      tperm.reserve(nt * 4);
-      tperm2.reserve(nt * 4);
-      tk32.reserve(nt * 4);
-      tk32b.reserve(nt * 4);
-      tk64.reserve(nt * 8);
-      tk64b.reserve(nt * 8);
-      fill_iota_u32(tperm.as<uint32_t>(), nt, 0, s);
-      // 1) by segment (key order)
-      SHD_HIP(hipMemcpyAsync(tk32.p, tSeg.p, nt * 4, hipMemcpyDeviceToDevice, s));
-      bool alt = false;
-      radix_sort_pairs_u32(tk32.as<uint32_t>(), tperm.as<uint32_t>(), tk32b.as<uint32_t>(), tperm2.as<uint32_t>(), nt,
-                           bits_for((uint64_t)nseg), d_sort, s, alt);
-      if (alt) SHD_HIP(hipMemcpyAsync(tperm.p, tperm2.p, nt * 4, hipMemcpyDeviceToDevice, s));
-      // 2) by notify head (signed -> order-preserving unsigned)
-      hipLaunchKernelGGL(k_xw_gather_u64, dim3(grid_cover(nt)), dim3(kBlock), 0, s, (const uint64_t*)tHead.as<uint64_t>(),
-                         (const uint32_t*)tperm.as<uint32_t>(), tk64.as<uint64_t>(), nt, 0x8000000000000000ull);
-      SHD_CHECK_LAUNCH();
-      alt = false;
-      radix_sort_pairs_u64(tk64.as<uint64_t>(), tperm.as<uint32_t>(), tk64b.as<uint64_t>(), tperm2.as<uint32_t>(), nt,
-                           64, d_sort, s, alt);
-      if (alt) SHD_HIP(hipMemcpyAsync(tperm.p, tperm2.p, nt * 4, hipMemcpyDeviceToDevice, s));
-      // 3) by call
-      hipLaunchKernelGGL(k_xw_gather_u32, dim3(grid_cover(nt)), dim3(kBlock), 0, s, (const uint32_t*)tF.as<uint32_t>(),
-                         (const uint32_t*)tperm.as<uint32_t>(), tk32.as<uint32_t>(), nt);
-      SHD_CHECK_LAUNCH();
-      alt = false;
-      radix_sort_pairs_u32(tk32.as<uint32_t>(), tperm.as<uint32_t>(), tk32b.as<uint32_t>(), tperm2.as<uint32_t>(), nt,
-                           bits_for((uint64_t)ncalls), d_sort, s, alt);
-      if (alt) SHD_HIP(hipMemcpyAsync(tperm.p, tperm2.p, nt * 4, hipMemcpyDeviceToDevice, s));
-      hipLaunchKernelGGL(k_xw_timer_rank, dim3(grid_cover(nt)), dim3(kBlock), 0, s, (const uint32_t*)tperm.as<uint32_t>(),
-                         (const int32_t*)tF.as<int32_t>(), nt, trank.as<uint32_t>(), sF.as<int32_t>());
-      SHD_CHECK_LAUNCH();
-    }
+    if (nt <= 0) return;
+    tperm.reserve(nt * 4);
+    tperm2.reserve(nt * 4);
+    tk32.reserve(nt * 4);
+    tk32b.reserve(nt * 4);
+    tk64.reserve(nt * 8);
+    tk64b.reserve(nt * 8);
+    fill_iota_u32(tperm.as<uint32_t>(), nt, 0, s);
+    // a stable sort's permutation, left in tperm
+    auto settle = [&](const uint32_t* perm) {
+      if (perm != tperm.as<uint32_t>()) SHD_HIP(hipMemcpyAsync(tperm.p, perm, nt * 4, hipMemcpyDeviceToDevice, s));
+    };
+    // 1) by segment (key order)
+    SHD_HIP(hipMemcpyAsync(tk32.p, tSeg.p, nt * 4, hipMemcpyDeviceToDevice, s));
+    settle(sort_u32(tk32, tperm, tk32b, tperm2, nt, bits_for((uint64_t)P.nseg), nullptr));
+    // 2) by notify head (signed -> order-preserving unsigned)
+    launch(k_xw_gather_u64, nt, tHead.as<uint64_t>(), tperm.as<uint32_t>(), tk64.as<uint64_t>(), nt,
+           0x8000000000000000ull);
+    settle(sort_u64(tk64, tperm, tk64b, tperm2, nt, 64, nullptr));
+    // 3) by call
+    launch(k_xw_gather_u32, nt, tF.as<uint32_t>(), tperm.as<uint32_t>(), tk32.as<uint32_t>(), nt);
+    settle(sort_u32(tk32, tperm, tk32b, tperm2, nt, bits_for((uint64_t)P.ncalls), nullptr));
+    launch(k_xw_timer_rank, nt, tperm.as<uint32_t>(), tF.as<int32_t>(), nt, trank.as<uint32_t>(), sF.as<int32_t>());
+  }
+
+  // sliding windows: the operations in key-major order
+  void sliding_operations(Push& P) {
+    hipStream_t s = stream;
+    const int64_t n = P.n, total = P.total;
     // partition runs before each call (chunk ordinals of timer chunks)
-    d_runs_before.reserve((size_t)ncalls * 8);
+    d_runs_before.reserve((size_t)P.ncalls * 8);
     if (partitioned && n > 0) {
-      hipLaunchKernelGGL(k_xw_runs_before, dim3(grid_cover(ncalls)), dim3(kBlock), 0, s, ncalls,
-                         (const int64_t*)d_offs.as<int64_t>(), n, (const uint32_t*)d_run.as<uint32_t>(),
-                         (uint64_t)nruns, d_runs_before.as<uint64_t>());
-      SHD_CHECK_LAUNCH();
+      launch(k_xw_runs_before, P.ncalls, P.ncalls, d_offs.as<int64_t>(), n, d_run.as<uint32_t>(), P.nruns,
+             d_runs_before.as<uint64_t>());
     } else if (partitioned) {
-      SHD_HIP(hipMemsetAsync(d_runs_before.p, 0, (size_t)ncalls * 8, s));
+      SHD_HIP(hipMemsetAsync(d_runs_before.p, 0, (size_t)P.ncalls * 8, s));
     }
-    // ---- operations in key-major order
     nops_b.reserve(std::max<int64_t>(total, 1) * 4);
     opscan.reserve(std::max<int64_t>(total, 1) * 4);
     if (total > 0) {
-      hipLaunchKernelGGL(k_xw_nops, dim3(grid_cover(total)), dim3(kBlock), 0, s, total, C, SP,
-                         (const uint64_t*)eopp.as<uint64_t>(), nops_b.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-      nops = scan(nops_b.as<uint32_t>(), opscan.as<uint32_t>(), total);
+      launch(k_xw_nops, total, total, C, P.SP, eopp.as<uint64_t>(), nops_b.as<uint32_t>());
+      P.nops = scan(nops_b.as<uint32_t>(), opscan.as<uint32_t>(), total);
     }
-    if (partitioned && n > 0 && nruns > 0) {
-      // run id (inclusive) of every keyed event: exclusive count + start - 1
-      d_start.reserve(n * 4);
-      run_ids(n);
-    }
-    reserve_ops(nops);
-    if (nops > 0) {
-      OpArgs oa{};
-      oa.total = total;
-      oa.C = C;
-      oa.sp = SP;
-      oa.segid = segid.as<uint32_t>();
-      oa.segS = segS.as<int64_t>();
-      oa.segCk = segCk.as<int64_t>();
-      oa.eopp = eopp.as<uint64_t>();
-      oa.etid = etid.as<uint32_t>();
-      oa.opscan = opscan.as<uint32_t>();
-      oa.irow = irow[cur].as<int32_t>();
-      oa.iseq = iseq[cur].as<int64_t>();
-      oa.call_of = d_call_of.as<int32_t>();
-      oa.call_now = d_call_now.as<int64_t>();
-      oa.run_of = partitioned ? d_start.as<uint32_t>() : nullptr;
-      oa.offs = d_offs.as<int64_t>();
-      oa.fnow_of_call = d_call_now.as<int64_t>();
-      oa.trank = trank.as<uint32_t>();
-      oa.sF = sF.as<int32_t>();
-      oa.nt = nt;
-      oa.runs_before = d_runs_before.as<uint64_t>();
-      oa.partitioned = partitioned;
-      oa.row_now = wkind == SHD_W_EXTERNAL_TIME ? reinterpret_cast<const int64_t*>(b.cs.col[wparam2]) : nullptr;
-      oa.current_on = plan.current_on;
-      oa.expired_on = plan.expired_on;
-      oa.seq0 = seq;
-      oa.op_item = op_item.as<uint32_t>();
-      oa.op_add = op_add.as<uint8_t>();
-      oa.op_on = op_on.as<uint8_t>();
-      oa.op_chunk = op_chunk.as<uint32_t>();
-      oa.op_now = op_now.as<int64_t>();
-      oa.op_seq = op_seq.as<int64_t>();
-      hipLaunchKernelGGL(k_xw_ops, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(oa));
-      SHD_CHECK_LAUNCH();
-    }
-    mark("operations");
-    }
-    const int64_t nop_alloc = std::max<int64_t>(nops, 1);
-    // ---- selector: aggregator folds and the rows each chunk emits
-    const int na = std::max(nagg, 1);
-    rowflag.reserve(nop_alloc);
-    rowsrc.reserve(nop_alloc * 4);
-    resv.reserve((size_t)na * nop_alloc * 8);
-    resn.reserve((size_t)na * nop_alloc);
-    FoldArgsX fa{};
-    fa.nagg = nagg;
-    for (int g = 0; g < nagg; g++) {
-      fa.kind[g] = plan.aggs[g].kind;
-      fa.type[g] = plan.aggs[g].type;
-    }
-    fa.group = group;
-    fa.cap = cap;
-    fa.nops = nops;
-    fa.nstates = nstates;
-    fa.argv = iargv[cur].as<uint64_t>();
-    fa.argn = iargn[cur].as<uint8_t>();
-    fa.op_item = op_item.as<uint32_t>();
-    fa.op_add = op_add.as<uint8_t>();
-    fa.op_on = op_on.as<uint8_t>();
-    fa.op_chunk = op_chunk.as<uint32_t>();
-    fa.op_now = op_now.as<int64_t>();
-    fa.its = its[cur].as<int64_t>();
-    fa.attr = iattr[cur].as<uint64_t>();
-    fa.nul = inul[cur].as<uint8_t>();
-    fa.ncols = ncols;
-    fa.es = dset();
-    fa.has_having = plan.having >= 0;
-    if (fa.has_having) fa.having = dexpr(plan.having);
-    fa.dsum = g_dsum.as<double>();
-    fa.lsum = g_lsum.as<int64_t>();
-    fa.cnt = g_cnt.as<int64_t>();
-    fa.epoch = (batch && nagg > 0) ? g_epoch.as<int64_t>() : nullptr;
-    fa.op_epoch = op_epoch.as<int64_t>();
-    fa.resv = resv.as<uint64_t>();
-    fa.resn = resn.as<uint8_t>();
-    fa.rowflag = rowflag.as<uint8_t>();
-    fa.rowsrc = rowsrc.as<uint32_t>();
-    int64_t nrows = 0;
-    if (nops > 0) {
-      const FoldArgsX* d_fa = dev_args(fa);
-      if (plain) {
-        hipLaunchKernelGGL(k_xw_plain_rows, dim3(grid_cover(nops)), dim3(kBlock), 0, s, d_fa);
-        SHD_CHECK_LAUNCH();
-      } else {
-        SHD_HIP(hipMemsetAsync(rowflag.p, 0, nops, s));
-        osid.reserve(nops * 4);
-        osid2.reserve(nops * 4);
-        oq.reserve(nops * 4);
-        oq2.reserve(nops * 4);
-        hipLaunchKernelGGL(k_xw_op_sid, dim3(grid_cover(nops)), dim3(kBlock), 0, s, nops,
-                           (const uint32_t*)op_item.as<uint32_t>(), (const uint64_t*)isid[cur].as<uint64_t>(),
-                           osid.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-        fill_iota_u32(oq.as<uint32_t>(), nops, 0, s);
-        bool alt = false;
-        radix_sort_pairs_u32(osid.as<uint32_t>(), oq.as<uint32_t>(), osid2.as<uint32_t>(), oq2.as<uint32_t>(), nops,
-                             bits_for((uint64_t)std::max<int64_t>(gd.count, 1)), d_sort, s, alt);
-        const uint32_t* ssid = alt ? osid2.as<uint32_t>() : osid.as<uint32_t>();
-        const uint32_t* sq = alt ? oq2.as<uint32_t>() : oq.as<uint32_t>();
-        ohead.reserve(nops * 4);
-        ohoff.reserve(nops * 4);
-        hipLaunchKernelGGL(k_xw_heads_u32, dim3(grid_cover(nops)), dim3(kBlock), 0, s, ssid, nops, ohead.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-        const int64_t nheads = scan(ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops);
-        ohl.reserve(std::max<int64_t>(nheads, 1) * 4);
-        hipLaunchKernelGGL(k_xw_head_list, dim3(grid_cover(nops)), dim3(kBlock), 0, s,
-                           (const uint32_t*)ohead.as<uint32_t>(), (const uint32_t*)ohoff.as<uint32_t>(), nops,
-                           ohl.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-        hipLaunchKernelGGL(k_xw_fold, dim3(grid_cover(nheads)), dim3(kBlock), 0, s, d_fa,
-                           (const uint32_t*)ohl.as<uint32_t>(), nheads, ssid, sq);
-        SHD_CHECK_LAUNCH();
-      }
-      mark("fold");
-      roff.reserve(nops * 4);
-      nrows = scan_u8_flags(rowflag.as<uint8_t>(), nops);
-    }
-    // ---- rows in (chunk, position) order
-    if (nrows > 0) {
-      rkey.reserve(nrows * 8);
-      rkey2.reserve(nrows * 8);
-      rq.reserve(nrows * 4);
-      rq2.reserve(nrows * 4);
-      hipLaunchKernelGGL(k_xw_row_keys, dim3(grid_cover(nops)), dim3(kBlock), 0, s, nops,
-                         (const uint8_t*)rowflag.as<uint8_t>(), (const uint32_t*)roff.as<uint32_t>(),
-                         (const uint32_t*)op_chunk.as<uint32_t>(), rkey.as<uint64_t>(), rq.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-      const int64_t nchunks = batch ? nflush : nt + (partitioned ? (int64_t)nruns : (int64_t)ncalls);
-      bool alt = false;
-      radix_sort_pairs_u64(rkey.as<uint64_t>(), rq.as<uint32_t>(), rkey2.as<uint64_t>(), rq2.as<uint32_t>(), nrows,
-                           32 + bits_for((uint64_t)nchunks), d_sort, s, alt);
-      const uint32_t* RQ = alt ? rq2.as<uint32_t>() : rq.as<uint32_t>();
-      out.ensure(nrows, s);
-      EmitArgsX ea{};
-      ea.es = dset();
-      ea.nout = (int)plan.outputs.size();
-      for (int c = 0; c < ea.nout; c++) ea.outs[c] = dexpr(plan.outputs[c].second);
-      ea.nagg = nagg;
-      ea.ncols = ncols;
-      ea.cap = cap;
-      ea.nops = nops;
-      ea.row0 = out.count;
-      ea.chunk0 = chunk_seq;
-      ea.rowsrc = rowsrc.as<uint32_t>();
-      ea.op_item = op_item.as<uint32_t>();
-      ea.op_add = op_add.as<uint8_t>();
-      ea.op_chunk = op_chunk.as<uint32_t>();
-      ea.op_now = op_now.as<int64_t>();
-      ea.op_seq = op_seq.as<int64_t>();
-      ea.its = its[cur].as<int64_t>();
-      ea.attr = iattr[cur].as<uint64_t>();
-      ea.nul = inul[cur].as<uint8_t>();
-      ea.resv = resv.as<uint64_t>();
-      ea.resn = resn.as<uint8_t>();
-      hipLaunchKernelGGL(k_xw_emit, dim3(grid_cover(nrows)), dim3(kBlock), 0, s, dev_args(ea), nrows, RQ, out.d_chunk(),
-                         out.d_type(), out.d_ts(), out.d_vals(), out.d_nulls(), out.d_seq(), out.d_sidx());
-      SHD_CHECK_LAUNCH();
-      out.count += nrows;
-    }
-    mark("emit");
-    // ---- carry: unexpired items (no window: nothing is kept; states persist)
-    int64_t kept = 0;
-    const int oth = cur ^ 1;
-    if (total > 0) {
-      keep.reserve(total * 4);
-      koff.reserve(total * 4);
-      if (batch) {
-        hipLaunchKernelGGL(k_xw_widen, dim3(grid_cover(total)), dim3(kBlock), 0, s,
-                           (const uint8_t*)xb_keep.as<uint8_t>(), total, keep.as<uint32_t>());
-      } else {
-        hipLaunchKernelGGL(k_xw_keep, dim3(grid_cover(total)), dim3(kBlock), 0, s, total,
-                           (const uint64_t*)eopp.as<uint64_t>(), wkind != 0 ? 1 : 0, keep.as<uint32_t>());
-      }
-      SHD_CHECK_LAUNCH();
-      kept = scan(keep.as<uint32_t>(), koff.as<uint32_t>(), total);
-    }
-    if (kept > 0) {
-      if (icap[oth] < std::max<int64_t>(kept, 1024)) alloc_slot(oth, std::max<int64_t>(kept * 2, 1024));
-      CarryArgs ca{};
-      ca.total = total;
-      ca.cap_src = cap;
-      ca.cap_dst = icap[oth];
-      ca.ncols = ncols;
-      ca.nagg = nagg;
-      ca.sp = SP;
-      ca.keep = keep.as<uint32_t>();
-      ca.koff = koff.as<uint32_t>();
-      ca.segid = segid.as<uint32_t>();
-      ca.last_out = lane_ran ? last_out.as<int64_t>() : nullptr;
-      ca.last_j = batch ? xb_last.as<int64_t>() : nullptr;
-      ca.pk = ipk[cur].as<uint64_t>(); ca.ts = its[cur].as<int64_t>(); ca.seq = iseq[cur].as<int64_t>();
-      ca.sid = isid[cur].as<uint64_t>();
-      ca.attr = iattr[cur].as<uint64_t>(); ca.nul = inul[cur].as<uint8_t>();
-      ca.argv = iargv[cur].as<uint64_t>(); ca.argn = iargn[cur].as<uint8_t>();
-      ca.d_pk = ipk[oth].as<uint64_t>(); ca.d_ts = its[oth].as<int64_t>(); ca.d_seq = iseq[oth].as<int64_t>();
-      ca.d_sid = isid[oth].as<uint64_t>(); ca.d_last = ilast[oth].as<int64_t>();
-      ca.d_call = icall[oth].as<int32_t>(); ca.d_row = irow[oth].as<int32_t>();
-      ca.d_attr = iattr[oth].as<uint64_t>(); ca.d_nul = inul[oth].as<uint8_t>();
-      ca.d_argv = iargv[oth].as<uint64_t>(); ca.d_argn = iargn[oth].as<uint8_t>();
-      hipLaunchKernelGGL(k_xw_carry, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(ca));
-      SHD_CHECK_LAUNCH();
-    }
-    // time windows: notify entries still queued, the window's last time
-    if (time_like() && timers) update_pending(nseg, nf, lane_ran);
-    if (time_like() && !partitioned && lane_ran && nseg > 0) {
-      tot.reserve();
-      SHD_HIP(hipMemcpyAsync(&tot.host().last_out, last_out.p, 8, hipMemcpyDeviceToHost, s));
-      SHD_HIP(hipStreamSynchronize(s));
-      last_global = tot.host().last_out;
-    }
-    cur = oth;
-    C = kept;
-    mark("carry");
-    SHD_HIP(hipEventRecord(ev1, s));
-    stage_end();
-    SHD_HIP(hipEventSynchronize(ev1));
-    float ms = 0.f;
-    SHD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
-    counters.kernel_ns = (int64_t)(ms * 1e6);
-    counters.kernel_ns_total += counters.kernel_ns;
-    counters.events += n;
-    counters.matches += nrows;
-    counters.carry = C;
-    counters.partial_scans += nops;
-    chunk_seq += batch ? nflush : nt + (partitioned ? (int64_t)nruns : (int64_t)ncalls);
-    now = clk;
-    seq += n;
+    if (partitioned && n > 0 && P.nruns > 0) run_ids(n);
+    reserve_ops(P.nops);
+    if (P.nops <= 0) return;
+    OpArgs oa{};
+    oa.total = total;
+    oa.C = C;
+    oa.sp = P.SP;
+    oa.segid = segid.as<uint32_t>();
+    oa.segS = segS.as<int64_t>();
+    oa.segCk = segCk.as<int64_t>();
+    oa.eopp = eopp.as<uint64_t>();
+    oa.etid = etid.as<uint32_t>();
+    oa.opscan = opscan.as<uint32_t>();
+    oa.irow = P.it.row;
+    oa.iseq = P.it.seq;
+    oa.call_of = d_call_of.as<int32_t>();
+    oa.call_now = d_call_now.as<int64_t>();
+    oa.run_of = partitioned ? d_start.as<uint32_t>() : nullptr;
+    oa.offs = d_offs.as<int64_t>();
+    oa.fnow_of_call = d_call_now.as<int64_t>();
+    oa.trank = trank.as<uint32_t>();
+    oa.sF = sF.as<int32_t>();
+    oa.nt = P.nt;
+    oa.runs_before = d_runs_before.as<uint64_t>();
+    oa.partitioned = partitioned;
+    oa.row_now = wkind == SHD_W_EXTERNAL_TIME ? reinterpret_cast<const int64_t*>(P.b.cs.col[wparam2]) : nullptr;
+    oa.current_on = plan.current_on;
+    oa.expired_on = plan.expired_on;
+    oa.seq0 = seq;
+    oa.op_item = op_item.as<uint32_t>();
+    oa.op_add = op_add.as<uint8_t>();
+    oa.op_on = op_on.as<uint8_t>();
+    oa.op_chunk = op_chunk.as<uint32_t>();
+    oa.op_now = op_now.as<int64_t>();
+    oa.op_seq = op_seq.as<int64_t>();
+    launch(k_xw_ops, total, dev_args(oa));
   }
 
   void reserve_ops(int64_t nops) {
@@ -2294,35 +2061,29 @@ struct WindowXEngine : Engine {
   // Batch windows: the push's output chunks (ordinals 0..nflush-1 in output
   // order: flushes, or every event / call in the stream modes), each item's
   // add / expiry chunk and RESET epoch, the operations in key-major order
-  // (k_xb_ops).  Returns the operation count.
-  int64_t batch_operations(int64_t n, int64_t m, int64_t total, int ncalls, int64_t nseg,
-                           const std::vector<char>& moved, const uint32_t* SP, int64_t& nflush) {
-    hipStream_t s = stream;
-    const int64_t ta = std::max<int64_t>(total, 1);
+  // (k_xb_ops).
+  void batch_operations(Push& P) {
+    const int64_t total = P.total, ta = std::max<int64_t>(total, 1);
     xb_added.reserve(ta);
     xb_aopp.reserve(ta * 8);
     eopp.reserve(ta * 8);
     xb_epoch.reserve(ta * 8);
     xb_keep.reserve(ta);
     xb_last.reserve(ta * 8);
-    if (total > 0) {
-      hipLaunchKernelGGL(k_xb_added, dim3(grid_cover(total)), dim3(kBlock), 0, s, total, C, SP,
-                         (const int64_t*)ilast[cur].as<int64_t>(), xb_added.as<uint8_t>());
-      SHD_CHECK_LAUNCH();
-    }
+    if (total > 0) launch(k_xb_added, total, total, C, P.SP, P.it.last, xb_added.as<uint8_t>());
     XbArgs xb{};
     xb.total = total;
     xb.C = C;
     xb.L = std::max<int64_t>(wparam, 1);
     xb.expired_on = plan.expired_on;
-    xb.sp = SP;
+    xb.sp = P.SP;
     xb.segid = segid.as<uint32_t>();
     xb.segS = segS.as<int64_t>();
     xb.segCk = segCk.as<int64_t>();
     xb.added_j = xb_added.as<uint8_t>();
-    xb.irow = irow[cur].as<int32_t>();
-    xb.icall = icall[cur].as<int32_t>();
-    xb.ilast = ilast[cur].as<int64_t>();
+    xb.irow = P.it.row;
+    xb.icall = P.it.call;
+    xb.ilast = P.it.last;
     xb.chunk0 = chunk_seq;
     xb.first_flush = -1;
     xb.aopp = xb_aopp.as<uint64_t>();
@@ -2330,175 +2091,162 @@ struct WindowXEngine : Engine {
     xb.epoch_j = xb_epoch.as<int64_t>();
     xb.keep_j = xb_keep.as<uint8_t>();
     xb.last_j = xb_last.as<int64_t>();
-    nflush = 0;
-    if (bmode == XB_FULL_LEN) {
-      // lengthBatch: a flush per completed batch, ranked by its trigger row
-      xb_trig.reserve(std::max<int64_t>(n, 1) * 4);
-      xb_fr.reserve(std::max<int64_t>(n, 1) * 4);
-      if (n > 0) SHD_HIP(hipMemsetAsync(xb_trig.p, 0, n * 4, s));
-      if (total > 0) {
-        hipLaunchKernelGGL(k_xb_len_trig, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(xb),
-                           xb_trig.as<uint32_t>());
-        SHD_CHECK_LAUNCH();
-      }
-      nflush = n > 0 ? scan(xb_trig.as<uint32_t>(), xb_fr.as<uint32_t>(), n) : 0;
-      xb_fnow.reserve(std::max<int64_t>(nflush, 1) * 8);
-      xb_fseq.reserve(std::max<int64_t>(nflush, 1) * 8);
-      if (nflush > 0) {
-        hipLaunchKernelGGL(k_xb_len_flushes, dim3(grid_cover(n)), dim3(kBlock), 0, s, n,
-                           (const uint32_t*)xb_trig.as<uint32_t>(), (const uint32_t*)xb_fr.as<uint32_t>(),
-                           (const int32_t*)d_call_of.as<int32_t>(), (const int64_t*)d_call_now.as<int64_t>(), seq,
-                           xb_fnow.as<int64_t>(), xb_fseq.as<int64_t>());
-        SHD_CHECK_LAUNCH();
-      }
-      xb.fr = xb_fr.as<uint32_t>();
-    } else if (bmode == XB_FULL_EXT) {
-      nflush = ext_flushes(n, total, nseg, SP, xb);
-    } else if (bmode == XB_STREAM_LEN || bmode == XB_ZERO_LEN) {
-      // an output chunk per event (its rank among the push's new items)
-      nflush = m;
-      xb_fnow.reserve(std::max<int64_t>(m, 1) * 8);
-      xb_fseq.reserve(std::max<int64_t>(m, 1) * 8);
-      if (m > 0) {
-        hipLaunchKernelGGL(k_xb_item_chunks, dim3(grid_cover(m)), dim3(kBlock), 0, s, C, m,
-                           (const int32_t*)icall[cur].as<int32_t>(), (const int32_t*)irow[cur].as<int32_t>(),
-                           (const int64_t*)d_call_now.as<int64_t>(), seq, xb_fnow.as<int64_t>(),
-                           xb_fseq.as<int64_t>());
-        SHD_CHECK_LAUNCH();
-      }
-    } else {
-      // timeBatch: the flush schedule is sequential in the chunks (calls and
-      // TIMER chunks), not in the events: run it on the host per call
-      xb_ccount.reserve((size_t)ncalls * 4);
-      xb_clast.reserve((size_t)ncalls * 8);
-      SHD_HIP(hipMemsetAsync(xb_ccount.p, 0, (size_t)ncalls * 4, s));
-      if (m > 0) {
-        hipLaunchKernelGGL(k_xb_call_items, dim3(grid_cover(m)), dim3(kBlock), 0, s, C, m,
-                           (const int32_t*)icall[cur].as<int32_t>(), (const int32_t*)irow[cur].as<int32_t>(), seq,
-                           xb_ccount.as<uint32_t>(), xb_clast.as<int64_t>());
-        SHD_CHECK_LAUNCH();
-      }
-      std::vector<uint32_t> cc(ncalls);
-      std::vector<int64_t> cl(ncalls);
-      h_pin.reserve((size_t)ncalls * 12);
-      SHD_HIP(hipMemcpyAsync(h_pin.p, xb_ccount.p, (size_t)ncalls * 4, hipMemcpyDeviceToHost, s));
-      SHD_HIP(hipMemcpyAsync(h_pin.as<char>() + (size_t)ncalls * 4, xb_clast.p, (size_t)ncalls * 8,
-                             hipMemcpyDeviceToHost, s));
-      SHD_HIP(hipStreamSynchronize(s));
-      std::memcpy(cc.data(), h_pin.p, (size_t)ncalls * 4);
-      std::memcpy(cl.data(), h_pin.as<char>() + (size_t)ncalls * 4, (size_t)ncalls * 8);
-      const bool stream_cur = bmode == XB_STREAM_TIME;
-      // per call: full batches -- the flush its events join; stream mode -- its
-      // chunk, the first flush at or after it, its RESET epoch
-      std::vector<int32_t> bfl(ncalls, -1), cch(ncalls, -1), cfl(ncalls, -1);
-      std::vector<int64_t> cep(ncalls, -1), fn, fs;
-      std::vector<int> pending;
-      auto flush_here = [&](int64_t t, int64_t sq) {   // a flush ends the current chunk list
-        const int32_t f = (int32_t)fn.size();
-        for (int pc : pending) (stream_cur ? cfl : bfl)[pc] = f;
-        pending.clear();
-        fn.push_back(t);
-        fs.push_back(sq);
-        if (stream_cur) tb_epoch = chunk_seq + f;   // RESET after this chunk's expirations
-      };
-      for (int c = 0; c < ncalls; c++) {
-        if (moved[c]) {
-          // Scheduler.sendTimerEvents (C/util/Scheduler.java:190-220): TIMER
-          // chunks while the queue head is due, each through the window
-          const int64_t t = h_now[c];
-          while (!tb_notify.empty() && tb_notify.front() <= t) {
-            tb_notify.pop_front();
-            if (tb_process(t)) {
-              if (xb.first_flush < 0) xb.first_flush = (int64_t)fn.size();
-              flush_here(t, seq + h_offs[c]);
-            }
-          }
-        }
-        if (cc[c] > 0) {   // a chunk of events reaches the window
-          pending.push_back(c);
-          const bool send = tb_process(h_now[c]);
-          if (stream_cur) {   // the call is a chunk of its own (its events stay in it)
-            cch[c] = (int32_t)fn.size();
-            cep[c] = tb_epoch;
-            fn.push_back(h_now[c]);
-            fs.push_back(cl[c]);
-            if (send) {   // expirations appended to the same chunk
-              for (int pc : pending) cfl[pc] = cch[c];
-              pending.clear();
-              if (xb.first_flush < 0) xb.first_flush = cch[c];
-              tb_epoch = chunk_seq + cch[c];
-            }
-          } else if (send) {
-            flush_here(h_now[c], cl[c]);
-          }
-        }
-      }
-      nflush = (int64_t)fn.size();
-      upload(xb_fnow, fn);
-      upload(xb_fseq, fs);
-      if (stream_cur) {
-        upload(xb_cchunk, cch);
-        upload(xb_cflush, cfl);
-        upload(xb_cepoch, cep);
-        xb.cchunk = xb_cchunk.as<int32_t>();
-        xb.cflush = xb_cflush.as<int32_t>();
-        xb.cepoch = xb_cepoch.as<int64_t>();
-      } else {
-        upload(xb_bflush, bfl);
-        xb.bflush = xb_bflush.as<int32_t>();
-        xb.nf = nflush;
-      }
-    }
-    if (total > 0) {
-      hipLaunchKernelGGL(k_xb_opp, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(xb), bmode);
-      SHD_CHECK_LAUNCH();
-    }
-    int64_t nops = 0;
+    if (bmode == XB_FULL_LEN) P.nflush = len_flushes(P, xb);
+    else if (bmode == XB_FULL_EXT) P.nflush = ext_flushes(P, xb);
+    else if (bmode == XB_STREAM_LEN || bmode == XB_ZERO_LEN) P.nflush = item_chunks(P);
+    else P.nflush = time_flushes(P, xb);
+    if (total > 0) launch(k_xb_opp, total, dev_args(xb), bmode);
     nops_b.reserve(ta * 4);
     opscan.reserve(ta * 4);
     if (total > 0) {
-      hipLaunchKernelGGL(k_xb_nops, dim3(grid_cover(total)), dim3(kBlock), 0, s, total,
-                         (const uint64_t*)xb_aopp.as<uint64_t>(), (const uint64_t*)eopp.as<uint64_t>(),
-                         nops_b.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-      nops = scan(nops_b.as<uint32_t>(), opscan.as<uint32_t>(), total);
+      launch(k_xb_nops, total, total, xb_aopp.as<uint64_t>(), eopp.as<uint64_t>(), nops_b.as<uint32_t>());
+      P.nops = scan(nops_b.as<uint32_t>(), opscan.as<uint32_t>(), total);
     }
-    reserve_ops(nops);
-    op_epoch.reserve(std::max<int64_t>(nops, 1) * 8);
-    if (nops > 0) {
-      XbOpArgs oa{};
-      oa.total = total;
-      oa.sp = SP;
-      oa.segid = segid.as<uint32_t>();
-      oa.segS = segS.as<int64_t>();
-      oa.segCk = segCk.as<int64_t>();
-      oa.added_j = xb_added.as<uint8_t>();
-      oa.aopp = xb_aopp.as<uint64_t>();
-      oa.eopp = eopp.as<uint64_t>();
-      oa.epoch_j = xb_epoch.as<int64_t>();
-      oa.full = bmode == XB_FULL_LEN || bmode == XB_FULL_TIME || bmode == XB_FULL_EXT;
-      oa.opscan = opscan.as<uint32_t>();
-      oa.fnow = xb_fnow.as<int64_t>();
-      oa.fseq = xb_fseq.as<int64_t>();
-      oa.current_on = plan.current_on;
-      oa.expired_on = plan.expired_on;
-      oa.op_epoch = op_epoch.as<int64_t>();
-      oa.op_item = op_item.as<uint32_t>();
-      oa.op_add = op_add.as<uint8_t>();
-      oa.op_on = op_on.as<uint8_t>();
-      oa.op_chunk = op_chunk.as<uint32_t>();
-      oa.op_now = op_now.as<int64_t>();
-      oa.op_seq = op_seq.as<int64_t>();
-      hipLaunchKernelGGL(k_xb_ops, dim3(grid_cover(total)), dim3(kBlock), 0, s, dev_args(oa));
-      SHD_CHECK_LAUNCH();
+    reserve_ops(P.nops);
+    op_epoch.reserve(std::max<int64_t>(P.nops, 1) * 8);
+    if (P.nops <= 0) return;
+    XbOpArgs oa{};
+    oa.total = total;
+    oa.sp = P.SP;
+    oa.segid = segid.as<uint32_t>();
+    oa.segS = segS.as<int64_t>();
+    oa.segCk = segCk.as<int64_t>();
+    oa.added_j = xb_added.as<uint8_t>();
+    oa.aopp = xb_aopp.as<uint64_t>();
+    oa.eopp = eopp.as<uint64_t>();
+    oa.epoch_j = xb_epoch.as<int64_t>();
+    oa.full = bmode == XB_FULL_LEN || bmode == XB_FULL_TIME || bmode == XB_FULL_EXT;
+    oa.opscan = opscan.as<uint32_t>();
+    oa.fnow = xb_fnow.as<int64_t>();
+    oa.fseq = xb_fseq.as<int64_t>();
+    oa.current_on = plan.current_on;
+    oa.expired_on = plan.expired_on;
+    oa.op_epoch = op_epoch.as<int64_t>();
+    oa.op_item = op_item.as<uint32_t>();
+    oa.op_add = op_add.as<uint8_t>();
+    oa.op_on = op_on.as<uint8_t>();
+    oa.op_chunk = op_chunk.as<uint32_t>();
+    oa.op_now = op_now.as<int64_t>();
+    oa.op_seq = op_seq.as<int64_t>();
+    launch(k_xb_ops, total, dev_args(oa));
+  }
+
+  // lengthBatch: a flush per completed batch, ranked by its trigger row.
+  // Returns the flush count, as the next three do.
+  int64_t len_flushes(Push& P, XbArgs& xb) {
+    const int64_t n = P.n;
+    xb_trig.reserve(std::max<int64_t>(n, 1) * 4);
+    xb_fr.reserve(std::max<int64_t>(n, 1) * 4);
+    if (n > 0) SHD_HIP(hipMemsetAsync(xb_trig.p, 0, n * 4, stream));
+    if (P.total > 0) launch(k_xb_len_trig, P.total, dev_args(xb), xb_trig.as<uint32_t>());
+    const int64_t nflush = n > 0 ? scan(xb_trig.as<uint32_t>(), xb_fr.as<uint32_t>(), n) : 0;
+    xb_fnow.reserve(std::max<int64_t>(nflush, 1) * 8);
+    xb_fseq.reserve(std::max<int64_t>(nflush, 1) * 8);
+    if (nflush > 0)
+      launch(k_xb_len_flushes, n, n, xb_trig.as<uint32_t>(), xb_fr.as<uint32_t>(), d_call_of.as<int32_t>(),
+             d_call_now.as<int64_t>(), seq, xb_fnow.as<int64_t>(), xb_fseq.as<int64_t>());
+    xb.fr = xb_fr.as<uint32_t>();
+    return nflush;
+  }
+
+  // lengthBatch stream / zero modes: an output chunk per event (its rank among the push's new items)
+  int64_t item_chunks(Push& P) {
+    const int64_t m = P.m;
+    xb_fnow.reserve(std::max<int64_t>(m, 1) * 8);
+    xb_fseq.reserve(std::max<int64_t>(m, 1) * 8);
+    if (m > 0)
+      launch(k_xb_item_chunks, m, C, m, P.it.call, P.it.row, d_call_now.as<int64_t>(), seq, xb_fnow.as<int64_t>(),
+             xb_fseq.as<int64_t>());
+    return m;
+  }
+
+  // timeBatch: the flush schedule is sequential in the chunks (calls and
+  // TIMER chunks), not in the events: run it on the host per call
+  int64_t time_flushes(Push& P, XbArgs& xb) {
+    hipStream_t s = stream;
+    const int ncalls = P.ncalls;
+    xb_ccount.reserve((size_t)ncalls * 4);
+    xb_clast.reserve((size_t)ncalls * 8);
+    SHD_HIP(hipMemsetAsync(xb_ccount.p, 0, (size_t)ncalls * 4, s));
+    if (P.m > 0)
+      launch(k_xb_call_items, P.m, C, P.m, P.it.call, P.it.row, seq, xb_ccount.as<uint32_t>(), xb_clast.as<int64_t>());
+    std::vector<uint32_t> cc(ncalls);
+    std::vector<int64_t> cl(ncalls);
+    h_pin.reserve((size_t)ncalls * 12);
+    SHD_HIP(hipMemcpyAsync(h_pin.p, xb_ccount.p, (size_t)ncalls * 4, hipMemcpyDeviceToHost, s));
+    SHD_HIP(hipMemcpyAsync(h_pin.as<char>() + (size_t)ncalls * 4, xb_clast.p, (size_t)ncalls * 8,
+                           hipMemcpyDeviceToHost, s));
+    SHD_HIP(hipStreamSynchronize(s));
+    std::memcpy(cc.data(), h_pin.p, (size_t)ncalls * 4);
+    std::memcpy(cl.data(), h_pin.as<char>() + (size_t)ncalls * 4, (size_t)ncalls * 8);
+    const bool stream_cur = bmode == XB_STREAM_TIME;
+    // per call: full batches -- the flush its events join; stream mode -- its
+    // chunk, the first flush at or after it, its RESET epoch
+    std::vector<int32_t> bfl(ncalls, -1), cch(ncalls, -1), cfl(ncalls, -1);
+    std::vector<int64_t> cep(ncalls, -1), fn, fs;
+    std::vector<int> pending;
+    auto flush_here = [&](int64_t t, int64_t sq) {   // a flush ends the current chunk list
+      const int32_t f = (int32_t)fn.size();
+      for (int pc : pending) (stream_cur ? cfl : bfl)[pc] = f;
+      pending.clear();
+      fn.push_back(t);
+      fs.push_back(sq);
+      if (stream_cur) tb_epoch = chunk_seq + f;   // RESET after this chunk's expirations
+    };
+    for (int c = 0; c < ncalls; c++) {
+      if (P.moved[c]) {
+        // Scheduler.sendTimerEvents (C/util/Scheduler.java:190-220): TIMER
+        // chunks while the queue head is due, each through the window
+        const int64_t t = h_now[c];
+        while (!tb_notify.empty() && tb_notify.front() <= t) {
+          tb_notify.pop_front();
+          if (tb_process(t)) {
+            if (xb.first_flush < 0) xb.first_flush = (int64_t)fn.size();
+            flush_here(t, seq + h_offs[c]);
+          }
+        }
+      }
+      if (cc[c] > 0) {   // a chunk of events reaches the window
+        pending.push_back(c);
+        const bool send = tb_process(h_now[c]);
+        if (stream_cur) {   // the call is a chunk of its own (its events stay in it)
+          cch[c] = (int32_t)fn.size();
+          cep[c] = tb_epoch;
+          fn.push_back(h_now[c]);
+          fs.push_back(cl[c]);
+          if (send) {   // expirations appended to the same chunk
+            for (int pc : pending) cfl[pc] = cch[c];
+            pending.clear();
+            if (xb.first_flush < 0) xb.first_flush = cch[c];
+            tb_epoch = chunk_seq + cch[c];
+          }
+        } else if (send) {
+          flush_here(h_now[c], cl[c]);
+        }
+      }
     }
-    return nops;
+    const int64_t nflush = (int64_t)fn.size();
+    upload(xb_fnow, fn);
+    upload(xb_fseq, fs);
+    if (stream_cur) {
+      upload(xb_cchunk, cch);
+      upload(xb_cflush, cfl);
+      upload(xb_cepoch, cep);
+      xb.cchunk = xb_cchunk.as<int32_t>();
+      xb.cflush = xb_cflush.as<int32_t>();
+      xb.cepoch = xb_cepoch.as<int64_t>();
+    } else {
+      upload(xb_bflush, bfl);
+      xb.bflush = xb_bflush.as<int32_t>();
+      xb.nf = nflush;
+    }
+    return nflush;
   }
 
   // externalTimeBatch: where the flushes fall (k_etb_*), ranked by trigger row;
-  // the keys' carried timing for the next push.  Returns the flush count.
-  int64_t ext_flushes(int64_t n, int64_t total, int64_t nseg, const uint32_t* SP, XbArgs& xb) {
-    hipStream_t s = stream;
+  // the keys' carried timing for the next push
+  int64_t ext_flushes(Push& P, XbArgs& xb) {
+    const int64_t n = P.n, total = P.total, nseg = P.nseg;
     xb_trig.reserve(std::max<int64_t>(n, 1) * 4);
     xb_fr.reserve(std::max<int64_t>(n, 1) * 4);
     xb_fnow.reserve(std::max<int64_t>(n, 1) * 8);
@@ -2516,12 +2264,12 @@ struct WindowXEngine : Engine {
     etb_seg_start.reserve(nseg * 8);
     etb_seg_end.reserve(nseg * 8);
     etb_seg_j1.reserve(nseg * 8);
-    if (n > 0) SHD_HIP(hipMemsetAsync(xb_trig.p, 0, n * 4, s));
+    if (n > 0) SHD_HIP(hipMemsetAsync(xb_trig.p, 0, n * 4, stream));
     EtbArgs ea{};
     ea.total = total;
     ea.C = C;
     ea.T = wparam;
-    ea.cap = icap[cur];
+    ea.cap = P.cap;
     ea.nseg = nseg;
     ea.seq0 = seq;
     ea.ts_col = etb_ts_col;
@@ -2529,16 +2277,16 @@ struct WindowXEngine : Engine {
     ea.start_col = etb_start_col;
     ea.replace = etb_replace;
     ea.start_const = etb_start_const;
-    ea.sp = SP;
+    ea.sp = P.SP;
     ea.segid = segid.as<uint32_t>();
     ea.segS = segS.as<int64_t>();
     ea.segCk = segCk.as<int64_t>();
     ea.pA = pA.as<int64_t>();
     ea.pB = pB.as<int64_t>();
     ea.pv = pv.as<int64_t>();
-    ea.irow = irow[cur].as<int32_t>();
-    ea.iattr = iattr[cur].as<uint64_t>();
-    ea.inul = inul[cur].as<uint8_t>();
+    ea.irow = P.it.row;
+    ea.iattr = P.it.attr;
+    ea.inul = P.it.nul;
     ea.M = etb_M.as<int64_t>();
     ea.head = etb_head.as<uint32_t>();
     ea.E = etb_E.as<int64_t>();
@@ -2548,45 +2296,28 @@ struct WindowXEngine : Engine {
     ea.seg_end = etb_seg_end.as<int64_t>();
     ea.seg_j1 = etb_seg_j1.as<int64_t>();
     const EtbArgs* d_ea = dev_args(ea);
-    hipLaunchKernelGGL(k_etb_seed, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
-    SHD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_etb_pmax_tiles, dim3((unsigned)nt), dim3(kBlock), 0, s, (const int64_t*)etb_M.as<int64_t>(),
-                       (const uint32_t*)etb_head.as<uint32_t>(), total, etb_tv.as<int64_t>(), etb_tf.as<uint32_t>());
-    SHD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_etb_pmax_scan, dim3(1), dim3(kBlock), 0, s, etb_tv.as<int64_t>(),
-                       (const uint32_t*)etb_tf.as<uint32_t>(), nt);
-    SHD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_etb_pmax_apply, dim3((unsigned)nt), dim3(kBlock), 0, s, etb_M.as<int64_t>(),
-                       (const uint32_t*)etb_head.as<uint32_t>(), total, (const int64_t*)etb_tv.as<int64_t>());
-    SHD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_etb_lane, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, d_ea);
-    SHD_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_etb_trig, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
-    SHD_CHECK_LAUNCH();
+    launch(k_etb_seed, total, d_ea);
+    launch_grid(k_etb_pmax_tiles, (unsigned)nt, etb_M.as<int64_t>(), etb_head.as<uint32_t>(), total,
+                etb_tv.as<int64_t>(), etb_tf.as<uint32_t>());
+    launch_grid(k_etb_pmax_scan, 1, etb_tv.as<int64_t>(), etb_tf.as<uint32_t>(), nt);
+    launch_grid(k_etb_pmax_apply, (unsigned)nt, etb_M.as<int64_t>(), etb_head.as<uint32_t>(), total,
+                etb_tv.as<int64_t>());
+    launch(k_etb_lane, nseg, d_ea);
+    launch(k_etb_trig, total, d_ea);
     // flushes in trigger-row order; per key, the triggers' sorted positions
     const int64_t nflush = n > 0 ? scan(xb_trig.as<uint32_t>(), xb_fr.as<uint32_t>(), n) : 0;
     scan(etb_trigj.as<uint32_t>(), etb_tjx.as<uint32_t>(), total);   // the same count, in key order
     if (nflush > 0) {
-      hipLaunchKernelGGL(k_xw_head_list, dim3(grid_cover(total)), dim3(kBlock), 0, s,
-                         (const uint32_t*)etb_trigj.as<uint32_t>(), (const uint32_t*)etb_tjx.as<uint32_t>(), total,
-                         etb_tpos.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
-      hipLaunchKernelGGL(k_etb_flushes, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea,
-                         (const uint32_t*)xb_fr.as<uint32_t>(), xb_fnow.as<int64_t>(), xb_fseq.as<int64_t>());
-      SHD_CHECK_LAUNCH();
+      launch(k_head_list, total, etb_trigj.as<uint32_t>(), etb_tjx.as<uint32_t>(), total, etb_tpos.as<uint32_t>());
+      launch(k_etb_flushes, total, d_ea, xb_fr.as<uint32_t>(), xb_fnow.as<int64_t>(), xb_fseq.as<int64_t>());
     }
     ppk2.reserve(nseg * 24);
     pv2.reserve(nseg * 24);
-    hipLaunchKernelGGL(k_etb_state, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, d_ea,
-                       (const uint64_t*)ipk[cur].as<uint64_t>(), ppk2.as<uint64_t>(), pv2.as<int64_t>());
-    SHD_CHECK_LAUNCH();
-    if (etb_replace) {
-      hipLaunchKernelGGL(k_etb_replace, dim3(grid_cover(total)), dim3(kBlock), 0, s, d_ea);
-      SHD_CHECK_LAUNCH();
-    }
-    SHD_HIP(hipStreamSynchronize(s));
-    std::swap(ppk.p, ppk2.p); std::swap(ppk.cap, ppk2.cap);
-    std::swap(pv.p, pv2.p); std::swap(pv.cap, pv2.cap);
+    launch(k_etb_state, nseg, d_ea, P.it.pk, ppk2.as<uint64_t>(), pv2.as<int64_t>());
+    if (etb_replace) launch(k_etb_replace, total, d_ea);
+    SHD_HIP(hipStreamSynchronize(stream));
+    ppk.swap(ppk2);
+    pv.swap(pv2);
     np = 3 * nseg;
     xb.fr = xb_fr.as<uint32_t>();
     xb.nf = nflush;
@@ -2596,58 +2327,209 @@ struct WindowXEngine : Engine {
     return nflush;
   }
 
-  // inclusive run id of each keyed event into d_start (k_xw_ops' run_of)
-  void run_ids(int64_t n) {
-    hipLaunchKernelGGL(k_xw_run_ids, dim3(grid_cover(n)), dim3(kBlock), 0, stream, n,
-                       (const uint32_t*)d_run.as<uint32_t>(), d_start.as<uint32_t>());
-    SHD_CHECK_LAUNCH();
-  }
+  // inclusive run id of each keyed event into d_start (k_xw_ops' run_of):
+  // exclusive count + own start - 1
+  void run_ids(int64_t n) { launch(k_xw_run_ids, n, n, d_run.as<uint32_t>(), d_start.as<uint32_t>()); }
 
   int64_t scan_u8_flags(const uint8_t* f, int64_t n) {
     nops_b.reserve(n * 4);
-    hipLaunchKernelGGL(k_xw_widen, dim3(grid_cover(n)), dim3(kBlock), 0, stream, f, n, nops_b.as<uint32_t>());
-    SHD_CHECK_LAUNCH();
+    launch(k_xw_widen, n, f, n, nops_b.as<uint32_t>());
     return scan(nops_b.as<uint32_t>(), roff.as<uint32_t>(), n);
   }
 
-  void update_pending(int64_t nseg, int nf, bool lane_ran) {
-    hipStream_t s = stream;
-    int64_t nseg_out = 0;
-    if (lane_ran && nseg > 0) {
-      nseg_out = scan(pcnt.as<uint32_t>(), pcnt_off.as<uint32_t>(), nseg);
+  // selector: aggregator folds and the rows each chunk emits
+  void push_fold(Push& P) {
+    const int64_t nops = P.nops, nop_alloc = std::max<int64_t>(nops, 1);
+    const int na = std::max(nagg, 1);
+    rowflag.reserve(nop_alloc);
+    rowsrc.reserve(nop_alloc * 4);
+    resv.reserve((size_t)na * nop_alloc * 8);
+    resn.reserve((size_t)na * nop_alloc);
+    if (nops <= 0) return;
+    FoldArgsX fa{};
+    fa.nagg = nagg;
+    for (int g = 0; g < nagg; g++) {
+      fa.kind[g] = plan.aggs[g].kind;
+      fa.type[g] = plan.aggs[g].type;
     }
-    // orphans: queued entries of keys without items in this push
+    fa.group = group;
+    fa.cap = P.cap;
+    fa.nops = nops;
+    fa.nstates = nstates;
+    fa.argv = P.it.argv;
+    fa.argn = P.it.argn;
+    fa.op_item = op_item.as<uint32_t>();
+    fa.op_add = op_add.as<uint8_t>();
+    fa.op_on = op_on.as<uint8_t>();
+    fa.op_chunk = op_chunk.as<uint32_t>();
+    fa.op_now = op_now.as<int64_t>();
+    fa.its = P.it.ts;
+    fa.attr = P.it.attr;
+    fa.nul = P.it.nul;
+    fa.ncols = ncols;
+    fa.es = dset();
+    fa.has_having = plan.having >= 0;
+    if (fa.has_having) fa.having = dexpr(plan.having);
+    fa.dsum = g_dsum.as<double>();
+    fa.lsum = g_lsum.as<int64_t>();
+    fa.cnt = g_cnt.as<int64_t>();
+    fa.epoch = (batch && nagg > 0) ? g_epoch.as<int64_t>() : nullptr;
+    fa.op_epoch = op_epoch.as<int64_t>();
+    fa.resv = resv.as<uint64_t>();
+    fa.resn = resn.as<uint8_t>();
+    fa.rowflag = rowflag.as<uint8_t>();
+    fa.rowsrc = rowsrc.as<uint32_t>();
+    const FoldArgsX* d_fa = dev_args(fa);
+    if (plain) {
+      launch(k_xw_plain_rows, nops, d_fa);
+    } else {
+      // one lane per state: the operations grouped by state id, in order
+      SHD_HIP(hipMemsetAsync(rowflag.p, 0, nops, stream));
+      osid.reserve(nops * 4);
+      osid2.reserve(nops * 4);
+      oq.reserve(nops * 4);
+      oq2.reserve(nops * 4);
+      launch(k_xw_op_sid, nops, nops, op_item.as<uint32_t>(), P.it.sid, osid.as<uint32_t>());
+      fill_iota_u32(oq.as<uint32_t>(), nops, 0, stream);
+      const uint32_t* ssid = nullptr;
+      const uint32_t* sq =
+          sort_u32(osid, oq, osid2, oq2, nops, bits_for((uint64_t)std::max<int64_t>(gd.count, 1)), &ssid);
+      ohead.reserve(nops * 4);
+      ohoff.reserve(nops * 4);
+      launch(k_seg_heads, nops, ssid, nops, ohead.as<uint32_t>());
+      const int64_t nheads = scan(ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops);
+      ohl.reserve(std::max<int64_t>(nheads, 1) * 4);
+      launch(k_head_list, nops, ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops, ohl.as<uint32_t>());
+      launch(k_xw_fold, nheads, d_fa, ohl.as<uint32_t>(), nheads, ssid, sq);
+    }
+    mark("fold");
+    roff.reserve(nops * 4);
+    P.nrows = scan_u8_flags(rowflag.as<uint8_t>(), nops);
+  }
+
+  // rows in (chunk, position) order
+  void push_emit(Push& P) {
+    const int64_t nrows = P.nrows, nops = P.nops;
+    if (nrows <= 0) return;
+    rkey.reserve(nrows * 8);
+    rkey2.reserve(nrows * 8);
+    rq.reserve(nrows * 4);
+    rq2.reserve(nrows * 4);
+    launch(k_xw_row_keys, nops, nops, rowflag.as<uint8_t>(), roff.as<uint32_t>(), op_chunk.as<uint32_t>(),
+           rkey.as<uint64_t>(), rq.as<uint32_t>());
+    const uint32_t* RQ = sort_u64(rkey, rq, rkey2, rq2, nrows, 32 + bits_for((uint64_t)chunks(P)), nullptr);
+    out.ensure(nrows, stream);
+    EmitArgsX ea{};
+    ea.es = dset();
+    ea.nout = (int)plan.outputs.size();
+    for (int c = 0; c < ea.nout; c++) ea.outs[c] = dexpr(plan.outputs[c].second);
+    ea.nagg = nagg;
+    ea.ncols = ncols;
+    ea.cap = P.cap;
+    ea.nops = nops;
+    ea.row0 = out.count;
+    ea.chunk0 = chunk_seq;
+    ea.rowsrc = rowsrc.as<uint32_t>();
+    ea.op_item = op_item.as<uint32_t>();
+    ea.op_add = op_add.as<uint8_t>();
+    ea.op_chunk = op_chunk.as<uint32_t>();
+    ea.op_now = op_now.as<int64_t>();
+    ea.op_seq = op_seq.as<int64_t>();
+    ea.its = P.it.ts;
+    ea.attr = P.it.attr;
+    ea.nul = P.it.nul;
+    ea.resv = resv.as<uint64_t>();
+    ea.resn = resn.as<uint8_t>();
+    launch(k_xw_emit, nrows, dev_args(ea), nrows, RQ, out.d_chunk(), out.d_type(), out.d_ts(), out.d_vals(),
+           out.d_nulls(), out.d_seq(), out.d_sidx());
+    out.count += nrows;
+  }
+
+  // carry: unexpired items (no window: nothing is kept; states persist); time
+  // windows: the notify entries still queued and the window's last time
+  void push_carry(Push& P) {
+    const int64_t total = P.total;
+    int64_t kept = 0;
+    const int oth = items.cur ^ 1;
+    if (total > 0) {
+      keep.reserve(total * 4);
+      koff.reserve(total * 4);
+      if (batch) launch(k_xw_widen, total, xb_keep.as<uint8_t>(), total, keep.as<uint32_t>());
+      else launch(k_xw_keep, total, total, eopp.as<uint64_t>(), wkind != 0 ? 1 : 0, keep.as<uint32_t>());
+      kept = scan(keep.as<uint32_t>(), koff.as<uint32_t>(), total);
+    }
+    if (kept > 0) {
+      if (items.cap[oth] < std::max<int64_t>(kept, 1024)) items.alloc(oth, std::max<int64_t>(kept * 2, 1024));
+      CarryArgs ca{};
+      ca.total = total;
+      ca.cap_src = P.cap;
+      ca.cap_dst = items.cap[oth];
+      ca.ncols = ncols;
+      ca.nagg = nagg;
+      ca.sp = P.SP;
+      ca.keep = keep.as<uint32_t>();
+      ca.koff = koff.as<uint32_t>();
+      ca.segid = segid.as<uint32_t>();
+      ca.last_out = P.lane_ran ? last_out.as<int64_t>() : nullptr;
+      ca.last_j = batch ? xb_last.as<int64_t>() : nullptr;
+      ca.src = P.it;
+      ca.dst = items.ptrs(oth);
+      launch(k_xw_carry, total, dev_args(ca));
+    }
+    if (time_like() && P.timers) update_pending(P);
+    if (time_like() && !partitioned && P.lane_ran && P.nseg > 0) {
+      tot.reserve();
+      SHD_HIP(hipMemcpyAsync(&tot.host().last_out, last_out.p, 8, hipMemcpyDeviceToHost, stream));
+      SHD_HIP(hipStreamSynchronize(stream));
+      last_global = tot.host().last_out;
+    }
+    items.cur = oth;
+    C = kept;
+  }
+
+  void push_counters(Push& P) {
+    SHD_HIP(hipEventRecord(ev1, stream));
+    stage_end();
+    SHD_HIP(hipEventSynchronize(ev1));
+    float ms = 0.f;
+    SHD_HIP(hipEventElapsedTime(&ms, ev0, ev1));
+    counters.kernel_ns = (int64_t)(ms * 1e6);
+    counters.kernel_ns_total += counters.kernel_ns;
+    counters.events += P.n;
+    counters.matches += P.nrows;
+    counters.carry = C;
+    counters.partial_scans += P.nops;
+    chunk_seq += chunks(P);
+    now = P.clk;
+    seq += P.n;
+  }
+
+  // the notify entries still queued: the segments' remaining ones and the
+  // orphans (queued entries of keys without items in this push)
+  void update_pending(Push& P) {
+    hipStream_t s = stream;
+    const int64_t nseg = P.nseg;
+    int64_t nseg_out = 0;
+    if (P.lane_ran && nseg > 0) nseg_out = scan(pcnt.as<uint32_t>(), pcnt_off.as<uint32_t>(), nseg);
     okeep.reserve(std::max<int64_t>(np, 1) * 4);
     okoff.reserve(std::max<int64_t>(np, 1) * 4);
     seg_pk.reserve(std::max<int64_t>(nseg, 1) * 8);
     int64_t nork = 0;
     if (np > 0) {
-      if (nseg > 0) {
-        hipLaunchKernelGGL(k_xw_seg_pk, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, nseg,
-                           (const int64_t*)segS.as<int64_t>(), (const uint32_t*)sp.as<uint32_t>(),
-                           (const uint64_t*)ipk[cur].as<uint64_t>(), seg_pk.as<uint64_t>());
-        SHD_CHECK_LAUNCH();
-      }
-      hipLaunchKernelGGL(k_xw_orphans, dim3(grid_cover(np)), dim3(kBlock), 0, s, np, (const uint64_t*)ppk.as<uint64_t>(),
-                         (const int64_t*)pv.as<int64_t>(), nseg, (const uint64_t*)seg_pk.as<uint64_t>(), nf,
-                         (const int64_t*)d_fnow.as<int64_t>(), okeep.as<uint32_t>());
-      SHD_CHECK_LAUNCH();
+      if (nseg > 0) launch(k_xw_seg_pk, nseg, nseg, segS.as<int64_t>(), P.SP, P.it.pk, seg_pk.as<uint64_t>());
+      launch(k_xw_orphans, np, np, ppk.as<uint64_t>(), pv.as<int64_t>(), nseg, seg_pk.as<uint64_t>(), P.nf,
+             d_fnow.as<int64_t>(), okeep.as<uint32_t>());
       nork = scan(okeep.as<uint32_t>(), okoff.as<uint32_t>(), np);
     }
     const int64_t nn = nseg_out + nork;
     ppk2.reserve(std::max<int64_t>(nn, 1) * 8);
     pv2.reserve(std::max<int64_t>(nn, 1) * 8);
     if (nseg_out > 0)
-      hipLaunchKernelGGL(k_xw_pend_gather, dim3(grid_cover(nseg)), dim3(kBlock), 0, s, nseg,
-                         (const uint32_t*)proom_off.as<uint32_t>(), (const uint32_t*)pcnt.as<uint32_t>(),
-                         (const uint32_t*)pcnt_off.as<uint32_t>(), (const uint64_t*)pout_pk.as<uint64_t>(),
-                         (const int64_t*)pout_v.as<int64_t>(), ppk2.as<uint64_t>(), pv2.as<int64_t>());
+      launch(k_xw_pend_gather, nseg, nseg, proom_off.as<uint32_t>(), pcnt.as<uint32_t>(), pcnt_off.as<uint32_t>(),
+             pout_pk.as<uint64_t>(), pout_v.as<int64_t>(), ppk2.as<uint64_t>(), pv2.as<int64_t>());
     if (nork > 0)
-      hipLaunchKernelGGL(k_xw_pend_orphan_copy, dim3(grid_cover(np)), dim3(kBlock), 0, s, np,
-                         (const uint32_t*)okeep.as<uint32_t>(), (const uint32_t*)okoff.as<uint32_t>(), nseg_out,
-                         (const uint64_t*)ppk.as<uint64_t>(), (const int64_t*)pv.as<int64_t>(), ppk2.as<uint64_t>(),
-                         pv2.as<int64_t>());
-    SHD_CHECK_LAUNCH();
+      launch(k_xw_pend_orphan_copy, np, np, okeep.as<uint32_t>(), okoff.as<uint32_t>(), nseg_out, ppk.as<uint64_t>(),
+             pv.as<int64_t>(), ppk2.as<uint64_t>(), pv2.as<int64_t>());
     // both parts are key-sorted: one stable key sort merges them (values stay
     // in order inside a key: a key is in one part only)
     if (nseg_out > 0 && nork > 0) {
@@ -2658,21 +2540,15 @@ struct WindowXEngine : Engine {
       pend_tmp_v.reserve(nn * 8);
       fill_iota_u32(pend_idx.as<uint32_t>(), nn, 0, s);
       SHD_HIP(hipMemcpyAsync(pend_tmp_pk.p, ppk2.p, nn * 8, hipMemcpyDeviceToDevice, s));
-      bool alt = false;
-      radix_sort_pairs_u64(pend_tmp_pk.as<uint64_t>(), pend_idx.as<uint32_t>(), pend_key2.as<uint64_t>(),
-                           pend_idx2.as<uint32_t>(), nn, 64, d_sort, s, alt);
-      const uint32_t* perm = alt ? pend_idx2.as<uint32_t>() : pend_idx.as<uint32_t>();
-      hipLaunchKernelGGL(k_xw_gather_u64, dim3(grid_cover(nn)), dim3(kBlock), 0, s, (const uint64_t*)ppk2.as<uint64_t>(),
-                         perm, pend_tmp_pk.as<uint64_t>(), nn, 0ull);
-      hipLaunchKernelGGL(k_xw_gather_u64, dim3(grid_cover(nn)), dim3(kBlock), 0, s, (const uint64_t*)pv2.as<uint64_t>(),
-                         perm, pend_tmp_v.as<uint64_t>(), nn, 0ull);
-      SHD_CHECK_LAUNCH();
-      std::swap(ppk2.p, pend_tmp_pk.p); std::swap(ppk2.cap, pend_tmp_pk.cap);
-      std::swap(pv2.p, pend_tmp_v.p); std::swap(pv2.cap, pend_tmp_v.cap);
+      const uint32_t* perm = sort_u64(pend_tmp_pk, pend_idx, pend_key2, pend_idx2, nn, 64, nullptr);
+      launch(k_gather_u64, nn, ppk2.as<uint64_t>(), perm, pend_tmp_pk.as<uint64_t>(), nn);
+      launch(k_gather_u64, nn, pv2.as<uint64_t>(), perm, pend_tmp_v.as<uint64_t>(), nn);
+      ppk2.swap(pend_tmp_pk);
+      pv2.swap(pend_tmp_v);
     }
     SHD_HIP(hipStreamSynchronize(s));
-    std::swap(ppk.p, ppk2.p); std::swap(ppk.cap, ppk2.cap);
-    std::swap(pv.p, pv2.p); std::swap(pv.cap, pv2.cap);
+    ppk.swap(ppk2);
+    pv.swap(pv2);
     np = nn;
   }
 
@@ -2684,21 +2560,10 @@ struct WindowXEngine : Engine {
     w.put<int64_t>(np);
     w.put<int64_t>(last_global);
     w.put<int64_t>(nstates);
-    if (C > 0) {
-      w.dev(ipk[cur].p, C * 8);
-      w.dev(its[cur].p, C * 8);
-      w.dev(iseq[cur].p, C * 8);
-      w.dev(isid[cur].p, C * 8);
-      w.dev(ilast[cur].p, C * 8);
-      for (int c = 0; c < ncols; c++) {
-        w.dev(iattr[cur].as<uint64_t>() + c * icap[cur], C * 8);
-        w.dev(inul[cur].as<uint8_t>() + c * icap[cur], C);
-      }
-      for (int g = 0; g < nagg; g++) {
-        w.dev(iargv[cur].as<uint64_t>() + g * icap[cur], C * 8);
-        w.dev(iargn[cur].as<uint8_t>() + g * icap[cur], C);
-      }
-    }
+    if (C > 0)
+      items.each([&](int c, int sub) {
+        if (kItemCol[c].saved) w.dev(items.at(items.cur, c, sub), C * kItemCol[c].size);
+      });
     if (np > 0) {
       w.dev(ppk.p, np * 8);
       w.dev(pv.p, np * 8);
@@ -2723,25 +2588,13 @@ struct WindowXEngine : Engine {
     const int64_t np0 = r.get<int64_t>();
     last_global = r.get<int64_t>();
     const int64_t ns = r.get<int64_t>();
-    C = 0;
-    cur = 0;
+    items.cur = 0;
     if (c0 > 0) {
-      if (icap[0] < c0) alloc_slot(0, std::max<int64_t>(c0, 1024));
-      r.dev_into(ipk[0].p, c0 * 8);
-      r.dev_into(its[0].p, c0 * 8);
-      r.dev_into(iseq[0].p, c0 * 8);
-      r.dev_into(isid[0].p, c0 * 8);
-      r.dev_into(ilast[0].p, c0 * 8);
-      for (int c = 0; c < ncols; c++) {
-        r.dev_into(iattr[0].as<uint64_t>() + c * icap[0], c0 * 8);
-        r.dev_into(inul[0].as<uint8_t>() + c * icap[0], c0);
-      }
-      for (int g = 0; g < nagg; g++) {
-        r.dev_into(iargv[0].as<uint64_t>() + g * icap[0], c0 * 8);
-        r.dev_into(iargn[0].as<uint8_t>() + g * icap[0], c0);
-      }
-      SHD_HIP(hipMemsetAsync(icall[0].p, 0xFF, c0 * 4, stream));
-      SHD_HIP(hipMemsetAsync(irow[0].p, 0xFF, c0 * 4, stream));
+      if (items.cap[0] < c0) items.alloc(0, std::max<int64_t>(c0, 1024));
+      items.each([&](int c, int sub) {   // what is not saved means "carried": all ones
+        if (kItemCol[c].saved) r.dev_into(items.at(0, c, sub), c0 * kItemCol[c].size);
+        else SHD_HIP(hipMemsetAsync(items.at(0, c, sub), 0xFF, c0 * kItemCol[c].size, stream));
+      });
     }
     C = c0;
     np = np0;
@@ -2751,20 +2604,9 @@ struct WindowXEngine : Engine {
       r.dev_into(ppk.p, np * 8);
       r.dev_into(pv.p, np * 8);
     }
+    nstates = 0;
     if (nagg > 0 && ns > 0) {
-      nstates = 0;
-      ensure_states(ns);
-      if (nstates != ns) {   // restore into tables of exactly the saved size
-        g_dsum.release(); g_lsum.release(); g_cnt.release();
-        g_dsum.reserve((size_t)nagg * ns * 8);
-        g_lsum.reserve((size_t)nagg * ns * 8);
-        g_cnt.reserve((size_t)nagg * ns * 8);
-        if (batch) {
-          g_epoch.release();
-          g_epoch.reserve((size_t)ns * 8);
-        }
-        nstates = ns;
-      }
+      grow_states(ns);   // tables of exactly the saved size
       r.dev_into(g_dsum.p, (size_t)nagg * ns * 8);
       r.dev_into(g_lsum.p, (size_t)nagg * ns * 8);
       r.dev_into(g_cnt.p, (size_t)nagg * ns * 8);
@@ -2878,6 +2720,8 @@ std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why) {
   // state key words: (partition key, group words); none for one global state
   e->nw = e->plain ? 0 : (e->partitioned ? 1 : 0) + e->ngk;
   e->gd.nk = std::max(e->nw, 1);
+  e->items.nsub[SUB_ATTR] = e->ncols;
+  e->items.nsub[SUB_AGG] = e->nagg;
   return e;
 }
 

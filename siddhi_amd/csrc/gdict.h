@@ -233,10 +233,10 @@ struct GroupDict {
       SHD_CHECK_LAUNCH();
     }
     SHD_HIP(hipStreamSynchronize(s));
-    std::swap(tag.p, t.p); std::swap(tag.cap, t.cap);
-    std::swap(id.p, i.p); std::swap(id.cap, i.cap);
-    std::swap(kw.p, k.p); std::swap(kw.cap, k.cap);
-    std::swap(kn.p, n.p); std::swap(kn.cap, n.cap);
+    tag.swap(t);
+    id.swap(i);
+    kw.swap(k);
+    kn.swap(n);
     cap = c;
   }
 

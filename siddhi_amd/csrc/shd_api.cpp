@@ -290,13 +290,13 @@ void OutputBuffer::ensure(int64_t extra, hipStream_t s) {
     SHD_HIP(hipMemcpyAsync(x2.p, sidx.p, count * 4, hipMemcpyDeviceToDevice, s));
     SHD_HIP(hipStreamSynchronize(s));
   }
-  std::swap(chunk.p, c2.p); std::swap(chunk.cap, c2.cap);
-  std::swap(type.p, t2.p); std::swap(type.cap, t2.cap);
-  std::swap(ts.p, ts2.p); std::swap(ts.cap, ts2.cap);
-  std::swap(vals.p, v2.p); std::swap(vals.cap, v2.cap);
-  std::swap(nulls.p, n2.p); std::swap(nulls.cap, n2.cap);
-  std::swap(sidx.p, x2.p); std::swap(sidx.cap, x2.cap);
-  std::swap(seq.p, q2.p); std::swap(seq.cap, q2.cap);
+  chunk.swap(c2);
+  type.swap(t2);
+  ts.swap(ts2);
+  vals.swap(v2);
+  nulls.swap(n2);
+  sidx.swap(x2);
+  seq.swap(q2);
   cap = nc;
 }
 
@@ -312,8 +312,8 @@ void OutputBuffer::ensure_list(int64_t extra, hipStream_t s) {
     SHD_HIP(hipMemcpyAsync(n2.p, lnul.p, lcount, hipMemcpyDeviceToDevice, s));
     SHD_HIP(hipStreamSynchronize(s));
   }
-  std::swap(lvals.p, v2.p); std::swap(lvals.cap, v2.cap);
-  std::swap(lnul.p, n2.p); std::swap(lnul.cap, n2.cap);
+  lvals.swap(v2);
+  lnul.swap(n2);
   lcap = nc;
 }
 
