@@ -244,6 +244,10 @@ void scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* 
 // Stable LSD radix sort of (key, value) pairs over key bits [0, bits).
 void radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                           int64_t n, int bits, DevBuf& scratch, hipStream_t s, bool& result_in_alt);
+// Same, on the digits of (key - kbase) from digit bit shift0 up (see radix_sort_triples_u32).
+void radix_sort_pairs_u32_from(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, int64_t n,
+                               int bits, DevBuf& scratch, hipStream_t s, bool& result_in_alt, uint32_t kbase,
+                               int shift0);
 void radix_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt,
                           int64_t n, int bits, DevBuf& scratch, hipStream_t s, bool& result_in_alt);
 // Device-wide max of u64 keys (result to dev ptr).

@@ -28,6 +28,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "engine.h"
 #include "knobs.h"
@@ -120,6 +121,43 @@ __global__ __launch_bounds__(kBlock) void k_sorted_ts64(const ExtRows* __restric
                                                         int64_t* __restrict__ sts64) {
   const ExtRows& x = *xp;
   for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p = n) sts64[p] = x.ts(pv_row(spv[p]));
+}
+
+// Lean key sort: keyed_sort_pass0's per-slice time range of the pushed rows
+// (absolute, one entry per 1 << kKsSliceBits extended rows) folded into at
+// most kScanCoarse entries of 1 << cbits rows each, as 32-bit offsets from the
+// batch's first event (the lean scan runs only when every offset fits).  An
+// entry without a pushed row is (INT32_MAX, INT32_MIN); the scan never reads
+// one.  A gather from the fine table per candidate (1 MB, L2 hits) made the
+// scan 0.45 ms per step slower on P3: the scan keeps this one in LDS.
+__global__ __launch_bounds__(kBlock) void k_slice_coarsen(const ExtRows* __restrict__ xp,
+                                                          const int64_t* __restrict__ slice_t, int64_t nslice,
+                                                          int cbits, int32_t* __restrict__ ctab) {
+  const int64_t tbase = xp->batch.ts[0];
+  const int e = (int)blockIdx.x * kBlock + threadIdx.x;
+  if (e >= kScanCoarse) return;
+  const int64_t per = (int64_t)1 << (cbits - kKsSliceBits);
+  const int64_t s0 = e * per, s1 = s0 + per < nslice ? s0 + per : nslice;
+  int64_t lo = LLONG_MAX, hi = LLONG_MIN;
+  for (int64_t i = s0; i < s1; i++) {
+    const int64_t l = slice_t[i], h = slice_t[nslice + i];
+    lo = l < lo ? l : lo;
+    hi = h > hi ? h : hi;
+  }
+  ctab[e] = lo == LLONG_MAX ? INT32_MAX : (int32_t)(lo - tbase);
+  ctab[kScanCoarse + e] = hi == LLONG_MIN ? INT32_MIN : (int32_t)(hi - tbase);
+}
+
+// Lean key sort (keyed_sort.hip: the rows were sorted without their time
+// word) on a push that then takes a path reading the sorted 32-bit offsets:
+// rebuilt from the rows, as k_sorted_ts64 gathers the full times.
+__global__ __launch_bounds__(kBlock) void k_sorted_ts32(const ExtRows* __restrict__ xp,
+                                                        const uint32_t* __restrict__ spv, int64_t n,
+                                                        int32_t* __restrict__ sts32) {
+  const ExtRows& x = *xp;
+  const int64_t tbase = x.batch.ts[0];
+  for (int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x; p < n; p = n)
+    sts32[p] = (int32_t)(x.ts(pv_row(spv[p])) - tbase);
 }
 
 #include "pattern_walk.h"
@@ -276,6 +314,16 @@ constexpr uint32_t kRecDeferred = 0x80000000u;   // positions stay below 2^28
 // whole 256-B stores.  scnt: per sub-tile [0, nsub) open, [nsub, 2 nsub)
 // deferred, [2 nsub, 3 nsub) records.  Outcome bytes, resume positions,
 // ScanOut partials and the per-tile counts as k_forward_scan writes them.
+// LEAN (lean key sort: no sorted time word, ScanArgs::ctab instead, copied
+// into LDS): a candidate whose successor p + 1 is a pushed event of its key
+// is dead when the earliest pushed time of the successor's row slice lies
+// more than `within` after the latest time the candidate can have (its own
+// slice's latest pushed time; a carried partial: the latest carried time) -- then
+// tq - tsi > within >= 0 whatever the exact times, walk_partial's first step
+// (no time regression either).  A candidate whose successor is of another
+// key stays open as walk_partial leaves it.  Every other candidate reads its
+// exact time from its row and walks as before, over positions whose times
+// come from the rows (RowPos).  The records carry no time word.
 constexpr int kRecRing = 128;   // >= 63 waiting + 64 of one slice
 // orders the wave's own LDS writes before its reads (and the reverse)
 __device__ __forceinline__ void wave_lds_order() {
@@ -283,6 +331,7 @@ __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __restrict__ ap, int64_t n_ext,
                                                              int64_t tile, const uint32_t* __restrict__ skey32,
                                                              const uint32_t* __restrict__ spv,
@@ -304,10 +353,21 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
   const int64_t s1 = s0 + sub < t1 ? s0 + sub : t1;
   const int64_t tbase = a.x.batch.ts[0];
   const GlobalPos<false, false> ld{skey32, nullptr, spv, sts32, nullptr, tbase, a.partitioned};
+  const RowPos ldr{skey32, spv, a.x.carry.ts, a.x.batch.ts, a.x.C, a.partitioned};
+  __shared__ int32_t ctab[LEAN ? 2 * kScanCoarse : 1];
+  if constexpr (LEAN) {
+    const int nc = (int)((n_ext - 1) >> a.cbits) + 1;   // <= kScanCoarse
+    for (int i = threadIdx.x; i < nc; i += kBlock) {
+      ctab[i] = a.ctab[i];
+      ctab[kScanCoarse + i] = a.ctab[kScanCoarse + i];
+    }
+    __syncthreads();
+  }
+  constexpr int kRecPos = LEAN ? 2 : 3;   // ring row of the record's position
   const uint64_t below = ((uint64_t)1 << lane) - 1;
   uint32_t wrec = 0, wdef = 0;   // the wave's records / deferred positions so far (wave-uniform)
   uint32_t wout = 0;             // records already stored (a multiple of 64 until the end)
-  __shared__ uint32_t ring[kSubPerTile][4][kRecRing];
+  __shared__ uint32_t ring[kSubPerTile][LEAN ? 3 : 4][kRecRing];
   uint32_t (*rg)[kRecRing] = ring[w];
   // lane i stores waiting record wout + i to sub-tile slot wout + i
   auto flush = [&](uint32_t cnt) {
@@ -317,8 +377,8 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
       const int64_t o = s0 + wout + lane;
       rkey[o] = rg[0][sl];
       rpv[o] = rg[1][sl];
-      rts[o] = (int32_t)rg[2][sl];
-      rpos[o] = rg[3][sl];
+      if constexpr (!LEAN) rts[o] = (int32_t)rg[2][sl];
+      rpos[o] = rg[kRecPos][sl];
     }
     wave_lds_order();
   };
@@ -333,15 +393,47 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
       int64_t tq;
       uint64_t kq = 0;
       const int64_t q0 = p + 1 < n_ext ? p + 1 : n_ext - 1;
-      ld(p, pvp, tsi, k);
-      ld(q0, pq, tq, kq);
+      if constexpr (LEAN) {
+        pvp = spv[p];
+        pq = spv[q0];
+        k = skey32[p];
+        kq = skey32[q0];
+      } else {
+        ld(p, pvp, tsi, k);
+        ld(q0, pq, tq, kq);
+      }
       if (pv_flags(pvp) & F_CAND) {
         int64_t q = p + 1;
         int32_t j = -1;
         uint32_t fm = 0;
         int64_t ra = -1, rb = -1;
-        const uint8_t st = walk_partial<true, false, 1>(a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tsi,
-                                                        false, j, steps, viol, fm, ra, rb);
+        uint8_t st;
+        if constexpr (LEAN) {
+          const uint32_t fq = pv_flags(pq);
+          const int64_t ri = pv_row(pvp), rq = pv_row(pq);
+          if (q >= n_ext || (kq != k && !(fq & F_SKIP))) {
+            st = ST_OPEN;   // the end of the key's run
+          } else {
+            bool dead = false;
+            if (kq == k && (fq & F_NEW) && !(fq & F_SKIP)) {
+              const int64_t hi = ri >= a.x.C ? tbase + ctab[kScanCoarse + (ri >> a.cbits)] : a.carry_tmax;
+              const int64_t lo = tbase + ctab[rq >> a.cbits];
+              dead = lo > hi && (uint64_t)lo - (uint64_t)hi > (uint64_t)a.within;
+            }
+            if (dead) {
+              st = ST_DEAD;
+              steps++;
+            } else {
+              tsi = ldr.row_ts(ri);
+              tq = ldr.row_ts(rq);
+              st = walk_partial<true, false, 1>(a, es, n_ext, ldr, ri, k, tsi, q, pq, tq, kq, tsi, false, j, steps,
+                                                viol, fm, ra, rb);
+            }
+          }
+        } else {
+          st = walk_partial<true, false, 1>(a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tsi, false, j, steps,
+                                            viol, fm, ra, rb);
+        }
         if (st == ST_DEFER) {
           out = PS_DEFER;
           match_row[p] = (int32_t)q;   // resume position (< 2^28)
@@ -361,8 +453,8 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
       const uint32_t sl = (wrec + (uint32_t)__popcll(mrec & below)) & (kRecRing - 1);
       rg[0][sl] = (uint32_t)k;
       rg[1][sl] = pvp;
-      rg[2][sl] = (uint32_t)(int32_t)(tsi - tbase);
-      rg[3][sl] = (uint32_t)p | (def ? kRecDeferred : 0u);
+      if constexpr (!LEAN) rg[2][sl] = (uint32_t)(int32_t)(tsi - tbase);
+      rg[kRecPos][sl] = (uint32_t)p | (def ? kRecDeferred : 0u);
     }
     if (def) dlist[s0 + wdef + __popcll(mdef & below)] = (uint32_t)p;
     wrec += (uint32_t)__popcll(mrec);
@@ -895,7 +987,8 @@ __global__ __launch_bounds__(kBlock) void k_forward_resume(const ScanArgs* __res
 // (k_forward_scan_rec); doff is the exclusive prefix of their lengths, which
 // each thread searches for its sub-tile, and a walk that ends open adds to
 // its sub-tile's open count (sopen).
-template <bool K64, bool FAST, bool TS64, bool SUB = false>
+// ROWT: the positions' times come from the rows (RowPos: lean key sort).
+template <bool K64, bool FAST, bool TS64, bool SUB = false, bool ROWT = false>
 __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restrict__ ap, int64_t n_ext, int64_t tile,
                                                         int ntile, const uint32_t* __restrict__ skey32,
                                                         const uint64_t* __restrict__ skey64,
@@ -913,8 +1006,12 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
   const DExprSet es = a.es;
   uint64_t steps = 0, pruned = 0;
   uint32_t viol = 0;
-  const int64_t tbase = TS64 ? 0 : a.x.batch.ts[0];
-  const GlobalPos<K64, TS64> ld{skey32, skey64, spv, sts32, sts64, tbase, a.partitioned};
+  const int64_t tbase = (TS64 || ROWT) ? 0 : a.x.batch.ts[0];
+  typedef typename std::conditional<ROWT, RowPos, GlobalPos<K64, TS64>>::type Ld;
+  const Ld ld = [&] {
+    if constexpr (ROWT) return RowPos{skey32, spv, a.x.carry.ts, a.x.batch.ts, a.x.C, a.partitioned};
+    else return GlobalPos<K64, TS64>{skey32, skey64, spv, sts32, sts64, tbase, a.partitioned};
+  }();
   const int64_t cnt = *dcount;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * kBlock) {
     int sti = 0;   // SUB: the position's sub-tile
@@ -941,7 +1038,7 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
     uint32_t fm = 0;
     int64_t ra = -1, rb = -1;
     if (a.logical == 2) and_carried(a, pv_row(pvp), fm, ra, rb);
-    const uint8_t st = walk_partial<false, FAST, 1, GlobalPos<K64, TS64>, 0, false>(
+    const uint8_t st = walk_partial<false, FAST, 1, Ld, 0, false>(
         a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tq, true, j, steps, viol, fm, ra, rb, p);
     uint8_t out = PS_NONE;
     const int t = (int)(p / tile);
@@ -1565,6 +1662,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_list(const GatherArgs* __rest
 // ballot per slice), so the table is dense and in position order, as
 // k_open_list + k_gather_list leave it.  Key, ext row and time come from the
 // record; only the amask columns and a carried row's seq are row gathers.
+// LEAN: the records carry no time (lean key sort): it is a row gather too.
+template <bool LEAN>
 __global__ __launch_bounds__(kBlock) void k_gather_rec(const GatherArgs* __restrict__ ap, int64_t sub, int nsub,
                                                        const uint32_t* __restrict__ rkey,
                                                        const uint32_t* __restrict__ rpv,
@@ -1578,7 +1677,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_rec(const GatherArgs* __restr
   const int st = (int)blockIdx.x * kSubPerTile + (threadIdx.x >> 6);
   const int64_t base = (int64_t)st * sub;
   const uint32_t nrec = scnt[2 * (int64_t)nsub + st];
-  const int64_t tbase = gld(a.x.batch.ts, 0);
+  const int64_t tbase = LEAN ? 0 : gld(a.x.batch.ts, 0);
   const uint64_t below = ((uint64_t)1 << lane) - 1;
   int64_t o0 = soff[st];
   for (uint32_t i0 = 0; i0 < nrec; i0 += 64) {
@@ -1596,8 +1695,8 @@ __global__ __launch_bounds__(kBlock) void k_gather_rec(const GatherArgs* __restr
     const uint64_t mv = __ballot(valid);
     if (valid) {
       const int64_t o = o0 + __popcll(mv & below);
-      gather_open_row(a, o, pv_row(rpv[base + i]), a.partitioned ? (uint64_t)rkey[base + i] : 0, true, pend);
-      a.dts[o] = tbase + (int64_t)rts[base + i];
+      gather_open_row(a, o, pv_row(rpv[base + i]), a.partitioned ? (uint64_t)rkey[base + i] : 0, !LEAN, pend);
+      if constexpr (!LEAN) a.dts[o] = tbase + (int64_t)rts[base + i];
     }
     o0 += __popcll(mv);
   }
@@ -1769,6 +1868,8 @@ struct PatternEngine : Engine {
   // fused prepare + first key-sort pass (keyed_sort.hip): the host reads the
   // push aggregates while the first pass runs
   DevBuf d_kps;
+  DevBuf d_slice;   // lean key sort: the pushed rows' time range per row slice (keyed_sort_pass0)
+  DevBuf d_ctab;    // ... folded to at most kScanCoarse entries (ScanArgs::ctab)
   hipEvent_t ev_pg = nullptr, ev_pt = nullptr;
   // sorted times of this push's positions (finish: carried partials' times)
   const int32_t* fin_sts32 = nullptr;
@@ -1779,6 +1880,7 @@ struct PatternEngine : Engine {
     bool on = false;
     uint32_t *key = nullptr, *pv = nullptr, *pos = nullptr;
     int32_t* ts = nullptr;
+    bool lean = false;   // lean key sort: the records carry no time (ts unused)
     int64_t sub = 0;
     int nsub = 0;
   } fin_rec;
@@ -2104,20 +2206,39 @@ struct PatternEngine : Engine {
                        (key_type[slot] == SHD_T_STRING || key_type[slot] == SHD_T_INT) && n_ext >= 2 &&
                        (fs_force >= 0 ? fs_force != 0 : n_ext >= ((int64_t)1 << 20));
     KsInfo* d_ksi = &agg.dev()->ks;
+    // lean key sort (the rows sorted without their time word; KsInfo::lean):
+    // wherever the emitting scan can run as far as is known before the first
+    // pass -- the rest (sparse keys) k_ks_finish estimates on the device.
+    // SHD_LEAN_SORT: on every fused sort (a push that then takes another path
+    // rebuilds the sorted times: k_sorted_ts32 below); SHD_NO_LEAN_SORT: never
+    int lean_mode = KS_LEAN_OFF;
+    if (fused && !knob_on(Knob::NO_LEAN_SORT)) {
+      int m = 0;
+      const bool scan_lists = W != INT64_MAX && logical != 2 && !knob_on(Knob::TS64) &&
+                              !knob_on(Knob::NO_RESUME_LIST) && !knob_on(Knob::NO_SCAN_LISTS) &&
+                              knob_force(Knob::LOCKSTEP) <= 0 && (!knob_int(Knob::RESUME_MODE, m) || m == 0);
+      lean_mode = knob_on(Knob::LEAN_SORT) ? KS_LEAN_ON : (scan_lists ? KS_LEAN_AUTO : KS_LEAN_OFF);
+    }
+    bool lean = false;   // this push's sorted positions carry no time word
     if (fused) {
       // the key range (ev_pg) is all the remaining passes need; the pushed
       // rows' time aggregates and the candidate count arrive with the first
       // pass (ev_pt, into prep_pass0), read while the remaining passes run
       if (!ev_pg) SHD_HIP(hipEventCreateWithFlags(&ev_pg, hipEventDisableTiming));
       if (!ev_pt) SHD_HIP(hipEventCreateWithFlags(&ev_pt, hipEventDisableTiming));
-      keyed_sort_front(s, d_pa_args, pa, n_ext, d_kps, d_pa, d_ksi);
+      keyed_sort_front(s, d_pa_args, pa, n_ext, d_kps, d_pa, d_ksi, lean_mode, W);
       agg.fetch(&PatternTotals::prep, s);
+      if (lean_mode != KS_LEAN_OFF) {
+        agg.fetch(&PatternTotals::ks, s);
+        d_slice.reserve((size_t)2 * keyed_sort_slices(n_ext) * sizeof(int64_t));
+      }
       SHD_HIP(hipEventRecord(ev_pg, s));
       keyed_sort_pass0(s, d_pa_args, pa, fattr, n_ext, d_kps, d_ksi, d_k32.as<uint32_t>(), d_pv.as<uint32_t>(),
-                       d_ts.as<uint32_t>(), d_pa);
+                       d_ts.as<uint32_t>(), d_slice.as<int64_t>(), d_pa);
       SHD_HIP(hipMemcpyAsync(&h_agg.prep_pass0, d_pa, sizeof(PrepAgg), hipMemcpyDeviceToHost, s));
       SHD_HIP(hipEventRecord(ev_pt, s));
       SHD_HIP(hipEventSynchronize(ev_pg));
+      lean = lean_mode != KS_LEAN_OFF && h_agg.ks.lean != 0;
     } else if (fast1)
       hipLaunchKernelGGL(k_prepare<true>, dim3(nblk), dim3(kBlock), 0, s, d_pa_args, n_ext, (int64_t)nblk * kBlock,
                          d_k32.as<uint32_t>(), d_k64.as<uint64_t>(), d_pv.as<uint32_t>(), d_ts.as<int32_t>(),
@@ -2190,7 +2311,7 @@ struct PatternEngine : Engine {
         }
       }
       d_pv_alt.reserve(n_ext * 4);
-      d_ts_alt.reserve(n_ext * 4);
+      if (!lean) d_ts_alt.reserve(n_ext * 4);
       if (key64 && bits <= 32) {
         hipLaunchKernelGGL(k_narrow_keys, dim3(grid_for(n_ext)), dim3(kBlock), 0, s, d_k64.as<uint64_t>(),
                            d_k32.as<uint32_t>(), n_ext);
@@ -2205,7 +2326,7 @@ struct PatternEngine : Engine {
         if (fused)
           keyed_sort_rest(s, n_ext, bits, kbase, d_k32.as<uint32_t>(), d_pv.as<uint32_t>(), d_ts.as<uint32_t>(),
                           d_k32_alt.as<uint32_t>(), d_pv_alt.as<uint32_t>(), d_ts_alt.as<uint32_t>(), d_kps, d_sort,
-                          in_alt);
+                          in_alt, lean);
         else
           radix_sort_triples_u32(d_k32.as<uint32_t>(), d_pv.as<uint32_t>(), d_ts.as<uint32_t>(),
                                  d_k32_alt.as<uint32_t>(), d_pv_alt.as<uint32_t>(), d_ts_alt.as<uint32_t>(), n_ext,
@@ -2254,6 +2375,14 @@ struct PatternEngine : Engine {
     sa.hash_mask = hash_mask;
     const int64_t t_end = (int64_t)pg.ts_max;   // latest event of this push
     sa.t_end = t_end;
+    if (lean) {   // the first pass's slice time table, coarsened (read by the lean scan only)
+      int cbits = kKsSliceBits;
+      while (((n_ext - 1) >> cbits) >= kScanCoarse) cbits++;
+      d_ctab.reserve((size_t)2 * kScanCoarse * sizeof(int32_t));
+      sa.ctab = d_ctab.as<int32_t>();
+      sa.cbits = cbits;
+      sa.carry_tmax = (int64_t)pg.carry_tmax;
+    }
     const bool fast2 = sa.f2.fp.ok != 0 && (!logical || sa.f3.fp.ok != 0);
     // contiguous tiles of positions per block (compaction offsets per block)
     const int64_t tile = ceil_div(ceil_div(n_ext, nblk), kBlock) * kBlock;
@@ -2338,6 +2467,24 @@ struct PatternEngine : Engine {
     // itself emits those lists and the open partials' records (k_forward_scan_rec)
     // unless SHD_NO_SCAN_LISTS
     const bool slists = rlist && grouped && !hash_mask && !ts64 && logical != 2 && !knob_on(Knob::NO_SCAN_LISTS);
+    // lean key sort: the emitting scan reads the slice time table instead of
+    // sorted times; any other path gets the sorted 32-bit offsets rebuilt from
+    // the rows first (64-bit times were gathered above, k_sorted_ts64)
+    const bool lean_scan = lean && slists && !prune && W != INT64_MAX;
+    if (lean && !lean_scan && !ts64) {
+      d_ts.reserve(n_ext * 4);
+      d_ts_alt.reserve(n_ext * 4);
+      int32_t* ts_out = sorted_alt ? d_ts_alt.as<int32_t>() : d_ts.as<int32_t>();
+      hipLaunchKernelGGL(k_sorted_ts32, dim3(grid_cover(n_ext)), dim3(kBlock), 0, s, dev_args(x), spv, n_ext, ts_out);
+      SHD_CHECK_LAUNCH();
+      sts32 = ts_out;
+    }
+    if (lean_scan) {
+      sts32 = nullptr;
+      hipLaunchKernelGGL(k_slice_coarsen, dim3(kScanCoarse / kBlock), dim3(kBlock), 0, s, dev_args(x),
+                         (const int64_t*)d_slice.as<int64_t>(), keyed_sort_slices(n_ext), sa.cbits, d_ctab.as<int32_t>());
+      SHD_CHECK_LAUNCH();
+    }
     const int nlb = (int)std::max<int64_t>(1, std::min<int64_t>(1024, ceil_div(n_ext, (int64_t)64 * kBlock)));
     if (sa.bsum) {
       hipLaunchKernelGGL(k_block_sum, dim3(grid_for(ceil_div(n_ext, 64) * 64, 1, 4096)), dim3(kBlock), 0, s, d_sa,
@@ -2395,15 +2542,20 @@ struct PatternEngine : Engine {
         fin_rec.on = true;
         fin_rec.key = sorted_alt ? d_k32.as<uint32_t>() : d_k32_alt.as<uint32_t>();
         fin_rec.pv = sorted_alt ? d_pv.as<uint32_t>() : d_pv_alt.as<uint32_t>();
-        fin_rec.ts = sorted_alt ? d_ts.as<int32_t>() : d_ts_alt.as<int32_t>();
+        fin_rec.lean = lean_scan;
+        fin_rec.ts = lean_scan ? nullptr : (sorted_alt ? d_ts.as<int32_t>() : d_ts_alt.as<int32_t>());
         d_olist.reserve((size_t)n_ext * 4);
         d_dlist.reserve((size_t)n_ext * 4);
         fin_rec.pos = d_olist.as<uint32_t>();
         fin_rec.sub = tile / kSubPerTile;
         fin_rec.nsub = nsub;
-        hipLaunchKernelGGL(k_forward_scan_rec, dim3(ntile), dim3(kBlock), 0, s, d_sa, n_ext, tile, skey32, spv, sts32,
-                           d_match.as<int32_t>(), d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(),
-                           fin_rec.key, fin_rec.pv, fin_rec.ts, fin_rec.pos, d_dlist.as<uint32_t>(), d_scnt);
+#define SHD_LAUNCH_SCAN_REC(LEAN)                                                                                  \
+  hipLaunchKernelGGL(k_forward_scan_rec<LEAN>, dim3(ntile), dim3(kBlock), 0, s, d_sa, n_ext, tile, skey32, spv,    \
+                     sts32, d_match.as<int32_t>(), d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(),                     \
+                     d_blk.as<ScanOut>(), fin_rec.key, fin_rec.pv, fin_rec.ts, fin_rec.pos, d_dlist.as<uint32_t>(), \
+                     d_scnt)
+        if (lean_scan) SHD_LAUNCH_SCAN_REC(true); else SHD_LAUNCH_SCAN_REC(false);
+#undef SHD_LAUNCH_SCAN_REC
       } else {
         if (ts64) SHD_LAUNCH_SCAN(false, true, false); else SHD_LAUNCH_SCAN(false, false, false);
       }
@@ -2423,13 +2575,17 @@ struct PatternEngine : Engine {
         // then one lane per deferred walk
         uint32_t* d_ndef = &agg.dev()->n_deferred;
         scan_exclusive_u32(d_scnt + nsub, d_soff + nsub, nsub, d_ndef, d_scan, s);
-#define SHD_LAUNCH_RSUB(FAST)                                                                                      \
-  hipLaunchKernelGGL((k_resume_list<false, FAST, false, true>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile,  \
+#define SHD_LAUNCH_RSUB(FAST, ROWT)                                                                                \
+  hipLaunchKernelGGL((k_resume_list<false, FAST, false, true, ROWT>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile, \
                      ntile, skey32, skey64, spv, sts32, sts64, d_match.as<int32_t>(), d_mother.as<int32_t>(),      \
                      d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(), ntile,                       \
                      (const uint32_t*)d_dlist.as<uint32_t>(), (const uint32_t*)d_ndef,                             \
                      (const uint32_t*)(d_soff + nsub), nsub, fin_rec.sub, d_scnt)
-        if (fast2) SHD_LAUNCH_RSUB(true); else SHD_LAUNCH_RSUB(false);
+        if (lean_scan) {
+          if (fast2) SHD_LAUNCH_RSUB(true, true); else SHD_LAUNCH_RSUB(false, true);
+        } else {
+          if (fast2) SHD_LAUNCH_RSUB(true, false); else SHD_LAUNCH_RSUB(false, false);
+        }
 #undef SHD_LAUNCH_RSUB
       } else if (rlist) {
         // sparse keys: the deferred positions compacted into a list (per-tile
@@ -2612,12 +2768,13 @@ struct PatternEngine : Engine {
           ga.key_attr = -1;
         }
         if (fin_rec.on) {
-          hipLaunchKernelGGL(k_gather_rec, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga), fin_rec.sub, fin_rec.nsub,
-                             (const uint32_t*)fin_rec.key, (const uint32_t*)fin_rec.pv, (const int32_t*)fin_rec.ts,
-                             (const uint32_t*)fin_rec.pos,
-                             (const uint32_t*)(d_bcnt.as<uint32_t>() + 3 * ntile),
-                             (const uint32_t*)(d_boff.as<uint32_t>() + 3 * ntile),
-                             (const uint8_t*)d_pst.as<uint8_t>());
+#define SHD_LAUNCH_GATHER_REC(LEAN)                                                                               \
+  hipLaunchKernelGGL(k_gather_rec<LEAN>, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga), fin_rec.sub, fin_rec.nsub, \
+                     (const uint32_t*)fin_rec.key, (const uint32_t*)fin_rec.pv, (const int32_t*)fin_rec.ts,        \
+                     (const uint32_t*)fin_rec.pos, (const uint32_t*)(d_bcnt.as<uint32_t>() + 3 * ntile),           \
+                     (const uint32_t*)(d_boff.as<uint32_t>() + 3 * ntile), (const uint8_t*)d_pst.as<uint8_t>())
+          if (fin_rec.lean) SHD_LAUNCH_GATHER_REC(true); else SHD_LAUNCH_GATHER_REC(false);
+#undef SHD_LAUNCH_GATHER_REC
         } else {
           d_olist.reserve((size_t)n_open * 4);
           hipLaunchKernelGGL(k_open_list, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),

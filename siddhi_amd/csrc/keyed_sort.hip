@@ -53,6 +53,7 @@ namespace {
 constexpr int kKsRounds = 16;                 // rows per lane of the fused pass
 constexpr int kKsTile = kRsBlock * kKsRounds;   // 4096 rows per workgroup
 constexpr int kKsChunk = 64;                  // tiles per offsets workgroup
+static_assert(64 * kKsRounds == 1 << kKsSliceBits, "a wave's slice of the first pass is one time-table slice");
 
 // Count of first-pass digit d in tile t (rotated raw low-byte histogram; a
 // zero-width sort puts every row in digit 0 like the unfused path, which does
@@ -213,9 +214,17 @@ __global__ __launch_bounds__(256) void k_ks_chunk_sum(const uint32_t* __restrict
 }
 
 // Fold of the chunks' aggregates + the sort's key base / width
-// (engine_pattern.hip sort_push: offsets from kmin when that narrows the key).
+// (engine_pattern.hip sort_push: offsets from kmin when that narrows the key),
+// and the lean choice (KsInfo::lean).  KS_LEAN_AUTO: lean when a partial
+// expects fewer than 0.25 events of its key inside one `within` span -- the
+// estimate sort_push makes for the scan (e_key), with the pushed rows' time
+// span taken from the first and last row (the time range is only known after
+// the first pass, which this choice shapes; a wrong guess costs time, never
+// the result).
 __global__ __launch_bounds__(256) void k_ks_finish(const PrepAgg* __restrict__ cblk, int nch,
-                                                   PrepAgg* __restrict__ out, KsInfo* __restrict__ info) {
+                                                   PrepAgg* __restrict__ out, KsInfo* __restrict__ info,
+                                                   const PrepArgs* __restrict__ ap, int64_t n_ext, int lean_mode,
+                                                   int64_t within) {
   PrepAcc acc;
   for (int b = threadIdx.x; b < nch; b += 256) {
     const PrepAgg& x = cblk[b];
@@ -243,7 +252,17 @@ __global__ __launch_bounds__(256) void k_ks_finish(const PrepAgg* __restrict__ c
       bits = rb > 0 ? rb : 1;
       kb = (uint32_t)kmin;
     }
-    *info = KsInfo{kb, bits};
+    int lean = lean_mode == KS_LEAN_ON;
+    if (lean_mode == KS_LEAN_AUTO) {
+      const ColSet& b = ap->x.batch;
+      const long long t0 = b.ts[0], t1 = b.ts[b.n > 0 ? b.n - 1 : 0];
+      const double span = t1 > t0 ? (double)(t1 - t0) + 1.0 : 1.0;
+      const double ne = (double)n_ext;
+      const double per_w = ne * ((double)within + 1.0) / span < ne ? ne * ((double)within + 1.0) / span : ne;
+      const double nkeys = (double)(kmax - (r.kmin < kmax ? r.kmin : kmax)) + 1.0;
+      lean = per_w / nkeys < 0.25;
+    }
+    *info = KsInfo{kb, bits, lean, 0};
   }
 }
 
@@ -362,6 +381,7 @@ __global__ __launch_bounds__(kRsBlock) void k_ks_scatter0(const PrepArgs* __rest
                                                           const uint32_t* __restrict__ offs, int nb,
                                                           uint32_t* __restrict__ kout, uint32_t* __restrict__ vout,
                                                           uint32_t* __restrict__ wout,
+                                                          int64_t* __restrict__ slice_t, int64_t nslice,
                                                           PrepAgg* __restrict__ blk) {
   const PrepArgs& a = *ap;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -549,9 +569,21 @@ __global__ __launch_bounds__(kRsBlock) void k_ks_scatter0(const PrepArgs* __rest
   }
   const bool zero = in.bits == 0;
   const uint32_t kb = in.kb;
+  const bool lean = in.lean != 0;
+  if (lean) {
+    // the pushed rows' time range of this wave's slice (acc holds the lane's
+    // pushed rows only; no assumption on their order)
+    const long long lo = wave_min(acc.tmin), hi = wave_max(acc.tmax);
+    const int64_t b = wb >> kKsSliceBits;
+    if (lane == 0 && b < nslice) {
+      slice_t[b] = lo;
+      slice_t[nslice + b] = hi;
+    }
+  }
+  // lean: the time word is neither staged nor written
   rs_scatter_tile_fn<uint32_t, kKsRounds, true>(
       kv, pv, tv, n_ext, t0, wb, [zero, kb](uint32_t k) { return zero ? 0u : ((k - kb) & 255u); }, c, gr, 0u, kout,
-      vout, wout);
+      vout, wout, lean);
   prep_block_reduce<kRsBlock>(acc, blk, tile);
 }
 
@@ -624,6 +656,7 @@ int keyed_sort_f1_attr(const DFilters& f1, bool is_a) {
 }
 
 static int64_t ks_tiles(int64_t n_ext) { return (n_ext + kKsTile - 1) / kKsTile; }
+int64_t keyed_sort_slices(int64_t n_ext) { return (n_ext + (1 << kKsSliceBits) - 1) >> kKsSliceBits; }
 
 // scratch: hraw[nb][256] | offs[nb][256] | csum[nch][256] | cpre[nch][256] | dtot[256] |
 //          PrepAgg blk[nb] | PrepAgg cblk[nch]
@@ -650,7 +683,7 @@ static KsScratch ks_scratch(DevBuf& scratch, int64_t n_ext, bool reserve) {
 }
 
 void keyed_sort_front(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, int64_t n_ext, DevBuf& scratch,
-                      PrepAgg* d_pg, KsInfo* d_info) {
+                      PrepAgg* d_pg, KsInfo* d_info, int lean_mode, int64_t within) {
   const KsScratch k = ks_scratch(scratch, n_ext, true);
   const bool knul = pa.x.batch.nul[pa.key_col] != nullptr;
   if (knul)
@@ -661,7 +694,8 @@ void keyed_sort_front(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, i
   hipLaunchKernelGGL(k_ks_chunk_sum, dim3(k.nch), dim3(256), 0, s, (const uint32_t*)k.hraw, k.nb,
                      (const PrepAgg*)k.blk, k.csum, k.cblk);
   SHD_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_ks_finish, dim3(1), dim3(256), 0, s, (const PrepAgg*)k.cblk, k.nch, d_pg, d_info);
+  hipLaunchKernelGGL(k_ks_finish, dim3(1), dim3(256), 0, s, (const PrepAgg*)k.cblk, k.nch, d_pg, d_info,
+                     d_pa, n_ext, lean_mode, within);
   SHD_CHECK_LAUNCH();
 }
 
@@ -712,7 +746,7 @@ static KsF1 ks_f1(const DFilters& f1, int fattr, const ColSet& cs) {
 
 void keyed_sort_pass0(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, int fattr, int64_t n_ext,
                       DevBuf& scratch, const KsInfo* d_info, uint32_t* k32, uint32_t* pv, uint32_t* ts,
-                      PrepAgg* d_pg) {
+                      int64_t* slice_t, PrepAgg* d_pg) {
   const KsScratch k = ks_scratch(scratch, n_ext, false);
   hipLaunchKernelGGL(k_ks_chunk_scan, dim3(256), dim3(256), 0, s, (const uint32_t*)k.csum, k.nch, k.nb, d_info, n_ext,
                      k.cpre, k.dtot);
@@ -725,12 +759,13 @@ void keyed_sort_pass0(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, i
   const int fsz = fattr >= 0 ? type_size(pa.x.batch.type[fattr]) : 0;
   const KsF1 f1 = knob_on(Knob::KS_GENERIC_F1) ? KsF1{} : ks_f1(pa.f1, pa.is_a ? fattr : -1, pa.x.batch);
   const int nb = k.nb;
+  const int64_t nslice = keyed_sort_slices(n_ext);
   const uint32_t* hraw = k.hraw;
   const uint32_t* offs = k.offs;
   PrepAgg* blk = k.blk;   // k_ks_hist's partials were folded by k_ks_chunk_sum already
 #define SHD_KS_LAUNCH(FSZ, KN, FN, FK)                                                                               \
   hipLaunchKernelGGL((k_ks_scatter0<FSZ, KN, FN, FK>), dim3(nb), dim3(kRsBlock), 0, s, d_pa, n_ext, fattr, f1,      \
-                     d_info, hraw, offs, nb, k32, pv, ts, blk)
+                     d_info, hraw, offs, nb, k32, pv, ts, slice_t, nslice, blk)
 #define SHD_KS_LAUNCH_N(FSZ, FK)                             \
   do {                                                       \
     if (knul) {                                              \
@@ -765,11 +800,17 @@ void keyed_sort_pass0(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, i
 // software-pipelined pass kernel with tile-major offsets (the next tile's
 // loads issued before the current tile's ranking) was built and measured
 // slower on P3 (447 vs 300 us per 56 M-row pass).
+// lean: the two-word passes (k_rs_scatter<uint32_t, kRsRounds, false, false>:
+// 16 B per row instead of 24, and three workgroups per CU instead of two).
 void keyed_sort_rest(hipStream_t s, int64_t n_ext, int bits, uint32_t kb, uint32_t* k32, uint32_t* pv, uint32_t* ts,
                      uint32_t* k32_alt, uint32_t* pv_alt, uint32_t* ts_alt, DevBuf&, DevBuf& sort_scratch,
-                     bool& in_alt) {
+                     bool& in_alt, bool lean) {
   in_alt = false;
   if (bits <= 8) return;
+  if (lean) {
+    radix_sort_pairs_u32_from(k32, pv, k32_alt, pv_alt, n_ext, bits, sort_scratch, s, in_alt, kb, 8);
+    return;
+  }
   radix_sort_triples_u32(k32, pv, ts, k32_alt, pv_alt, ts_alt, n_ext, bits, sort_scratch, s, in_alt, false, kb, 8);
 }
 

@@ -149,6 +149,7 @@ struct F2Split {
   SplitCmp c[kSplitMax];
 };
 
+constexpr int kKsSliceBits = 10;   // 1024 extended rows: one wave's slice of the fused first pass (keyed_sort.hip)
 struct ScanArgs {
   ExtRows x;
   DExprSet es;
@@ -174,7 +175,17 @@ struct ScanArgs {
   const BlockSum* bsum;
   int bs_ci, bs_side, bs_op, bs_attr;
   F2Split sp;           // plain form: f2 split per comparison (sp.ok = 0: eval_fpred)
+  // lean key sort (k_forward_scan_rec<true>): the pushed rows' earliest
+  // ([0, kScanCoarse)) and latest ([kScanCoarse, 2 kScanCoarse)) time per
+  // 1 << cbits extended rows, as 32-bit offsets from the batch's first event
+  // (k_slice_coarsen folds keyed_sort_pass0's slice table into these: at
+  // most kScanCoarse entries, which every scan workgroup keeps in LDS), and
+  // the latest carried partial's time (PrepAgg::carry_tmax)
+  const int32_t* ctab;
+  int cbits;
+  int64_t carry_tmax;
 };
+constexpr int kScanCoarse = 2048;
 
 struct ScanOut {
   unsigned long long steps;   // (partial, event) pairs examined
@@ -360,11 +371,20 @@ __device__ __forceinline__ void prep_block_reduce(PrepAcc acc, PrepAgg* blk, int
 
 // Fused row preparation + first key-sort pass (keyed_sort.hip; partitioned
 // plans on a 32-bit plain key attribute).  KsInfo: the sort's key base and
-// width as sort_push derives them from the push's key range.
+// width as sort_push derives them from the push's key range, and whether the
+// sort is lean: the rows travel as (key, payload) pairs without the 32-bit
+// time word, and the first pass writes the pushed rows' time range per slice
+// of kKsSlice extended rows instead (k_ks_finish decides from the push's key
+// density; a choice of speed only -- sort_push rebuilds the sorted times from
+// the rows when the push then takes a path that reads them).
 struct KsInfo {
   uint32_t kb;
   int32_t bits;
+  int32_t lean;
+  int32_t pad_;
 };
+// lean_mode of keyed_sort_front: 0 never lean, 1 lean on sparse keys (the scan's own estimate), 2 always
+enum : int { KS_LEAN_OFF = 0, KS_LEAN_AUTO = 1, KS_LEAN_ON = 2 };
 
 // The pattern engine's per-push readback block (PatternEngine::agg).  The
 // device layout is fixed: prepare and scan each own a 64-byte slot, and the
@@ -384,7 +404,7 @@ struct PatternTotals {
 static_assert(offsetof(PatternTotals, prep) == 0 && offsetof(PatternTotals, scan) == 64 &&
                   offsetof(PatternTotals, n_match) == 128 && offsetof(PatternTotals, n_open) == 132 &&
                   offsetof(PatternTotals, tail_) + sizeof(uint32_t[2]) == 64 + 80 &&
-                  offsetof(PatternTotals, ks) == 232 && offsetof(PatternTotals, n_deferred) == 240 &&
+                  offsetof(PatternTotals, ks) == 232 && offsetof(PatternTotals, n_deferred) == 248 &&
                   sizeof(PatternTotals) <= 256,
               "PatternTotals device layout");
 // Host image: the device fields, then what only the host reads.
@@ -398,18 +418,25 @@ struct PatternTotalsHost : PatternTotals {
 int keyed_sort_f1_attr(const DFilters& f1, bool is_a);
 // hist + key range (d_pg: the push's PrepAgg with the key range only -- n_cand
 // 0, time fields unset: keyed_sort_pass0 completes them -- and d_info, the
-// sort's key base / width)
+// sort's key base / width and the lean choice: lean_mode KS_LEAN_*, within
+// the pattern's `within` for the density estimate)
 void keyed_sort_front(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, int64_t n_ext, DevBuf& scratch,
-                      PrepAgg* d_pg, KsInfo* d_info);
+                      PrepAgg* d_pg, KsInfo* d_info, int lean_mode, int64_t within);
 // first pass: rows sorted by the first digit into (k32, pv, ts); completes
-// d_pg (candidates created, time range / order / overflow, latest carried)
+// d_pg (candidates created, time range / order / overflow, latest carried).
+// A lean sort (d_info->lean) leaves ts unwritten and fills slice_t instead:
+// slice_t[b] / slice_t[nslice + b] = earliest / latest time of the pushed
+// rows among extended rows [b << kKsSliceBits, (b + 1) << kKsSliceBits)
+// (LLONG_MAX / LLONG_MIN: none), nslice = keyed_sort_slices(n_ext).
+int64_t keyed_sort_slices(int64_t n_ext);
 void keyed_sort_pass0(hipStream_t s, const PrepArgs* d_pa, const PrepArgs& pa, int fattr, int64_t n_ext,
                       DevBuf& scratch, const KsInfo* d_info, uint32_t* k32, uint32_t* pv, uint32_t* ts,
-                      PrepAgg* d_pg);
-// the remaining passes (digits from shift 8 to bits) of a fused sort
+                      int64_t* slice_t, PrepAgg* d_pg);
+// the remaining passes (digits from shift 8 to bits) of a fused sort; lean:
+// on (k32, pv) alone (ts / ts_alt unused)
 void keyed_sort_rest(hipStream_t s, int64_t n_ext, int bits, uint32_t kb, uint32_t* k32, uint32_t* pv, uint32_t* ts,
                      uint32_t* k32_alt, uint32_t* pv_alt, uint32_t* ts_alt, DevBuf& scratch, DevBuf& sort_scratch,
-                     bool& in_alt);
+                     bool& in_alt, bool lean);
 
 }  // namespace pat
 }  // namespace shd

@@ -30,6 +30,22 @@ struct GlobalPos {
     if (partitioned) kq = K64 ? skey64[q] : skey32[q];
   }
 };
+// The same after a lean key sort (32-bit keys; the sorted positions carry no
+// time word): the time is read from the event's own row.
+struct RowPos {
+  const uint32_t* __restrict__ skey32;
+  const uint32_t* __restrict__ spv;
+  const int64_t* __restrict__ carry_ts;
+  const int64_t* __restrict__ batch_ts;
+  int64_t C;
+  int partitioned;
+  __device__ __forceinline__ int64_t row_ts(int64_t r) const { return r < C ? gld(carry_ts, r) : gld(batch_ts, r - C); }
+  __device__ __forceinline__ void operator()(int64_t q, uint32_t& pq, int64_t& tq, uint64_t& kq) const {
+    pq = spv[q];
+    if (partitioned) kq = skey32[q];
+    tq = row_ts(pv_row(pq));
+  }
+};
 
 // Split f2 (F2Split): the per-partial side of every comparison, and the
 // step's evaluation against an e2 event (batch row r2b = ext row - C, sorted

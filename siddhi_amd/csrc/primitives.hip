@@ -296,6 +296,12 @@ void radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, ui
                                              in_alt);
 }
 
+void radix_sort_pairs_u32_from(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt, int64_t n,
+                               int bits, DevBuf& scratch, hipStream_t s, bool& in_alt, uint32_t kbase, int shift0) {
+  radix_sort_run<uint32_t, kRsRounds, false>(keys, vals, nullptr, keys_alt, vals_alt, nullptr, n, bits, scratch, s,
+                                             in_alt, kbase, shift0);
+}
+
 void radix_sort_pairs_u64(uint64_t* keys, uint32_t* vals, uint64_t* keys_alt, uint32_t* vals_alt, int64_t n,
                           int bits, DevBuf& scratch, hipStream_t s, bool& in_alt) {
   radix_sort_run<uint64_t, kRsRounds, false>(keys, vals, nullptr, keys_alt, vals_alt, nullptr, n, bits, scratch, s,

@@ -55,6 +55,8 @@ __device__ __forceinline__ uint32_t rs_hdigit(K k, int shift, K kb) {
 // offset inside the digit (gr) and the digit's total (dt); wave w holds rows
 // [wb, wb + 64R) of the tile starting at t0, R per lane (k, v, x; rows >= n
 // are padding).
+// no_w (P2 only, workgroup-uniform): the second payload is neither staged nor
+// written (the lean first pass of keyed_sort.hip decides that at run time).
 // dig(key) -> digit in [0, 256): rs_scatter_tile below takes the digits of
 // (key - kb) >> shift (or of the hashed key); the fused first pass of the
 // pattern engine's key sort (keyed_sort.hip) passes its own.
@@ -63,7 +65,7 @@ __device__ __forceinline__ void rs_scatter_tile_fn(const K (&k)[R], const uint32
                                                    const uint32_t (&x)[P2 ? R : 1], int64_t n, int64_t t0,
                                                    int64_t wb, const Dig& dig, uint32_t c, uint32_t gr, uint32_t dt,
                                                    K* __restrict__ kout, uint32_t* __restrict__ vout,
-                                                   uint32_t* __restrict__ wout) {
+                                                   uint32_t* __restrict__ wout, bool no_w = false) {
   constexpr int T = rs_tile(R);
   __shared__ K sk[T];
   __shared__ uint32_t sv[T];
@@ -144,7 +146,7 @@ __device__ __forceinline__ void rs_scatter_tile_fn(const K (&k)[R], const uint32
       const uint32_t pos = wcnt[w][dig(k[r])] + lr[r];
       sk[pos] = k[r];
       sv[pos] = v[r];
-      if (P2) sw[pos] = x[r];
+      if (P2 && !no_w) sw[pos] = x[r];
     }
   }
   __syncthreads();
@@ -156,7 +158,7 @@ __device__ __forceinline__ void rs_scatter_tile_fn(const K (&k)[R], const uint32
     const uint32_t o = gbase[d] + (uint32_t)i - lpre[d];
     kout[o] = kk;
     vout[o] = sv[i];
-    if (P2) wout[o] = sw[i];
+    if (P2 && !no_w) wout[o] = sw[i];
   }
 }
 
