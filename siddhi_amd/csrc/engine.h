@@ -234,6 +234,28 @@ struct Engine {
     }
     SHD_HIP(hipStreamSynchronize(stream));   // previous push's argument copies have landed
     arg_used = 0;
+    arg_staged = kNoneStaged;
+  }
+  // Argument blocks whose contents are known together travel in one copy:
+  // args_stage() places a block in the pinned arena (same 256-byte alignment)
+  // and returns its device address at once; args_send() then uploads
+  // everything staged since the last send, gaps included, with one
+  // hipMemcpyAsync.  A kernel reading a staged block is launched after the send.
+  static constexpr size_t kNoneStaged = ~size_t(0);
+  size_t arg_staged = kNoneStaged;   // arena offset of the first block not sent yet
+  template <class T> const T* args_stage(const T& a) {
+    size_t off = (arg_used + 255) & ~size_t(255);
+    if (!arg_dev.p || off + sizeof(T) > kArgArena) throw Error(SHD_E_CAPACITY, "kernel argument arena exhausted");
+    std::memcpy(arg_host.as<char>() + off, &a, sizeof(T));
+    if (arg_staged == kNoneStaged) arg_staged = off;
+    arg_used = off + sizeof(T);
+    return reinterpret_cast<const T*>(arg_dev.as<char>() + off);
+  }
+  void args_send() {
+    if (arg_staged == kNoneStaged) return;
+    SHD_HIP(hipMemcpyAsync(arg_dev.as<char>() + arg_staged, arg_host.as<char>() + arg_staged, arg_used - arg_staged,
+                           hipMemcpyHostToDevice, stream));
+    arg_staged = kNoneStaged;
   }
   template <class T> const T* dev_args(const T& a) {
     size_t off = (arg_used + 255) & ~size_t(255);

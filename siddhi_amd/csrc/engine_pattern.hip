@@ -331,7 +331,17 @@ __device__ __forceinline__ void wave_lds_order() {
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
-template <bool LEAN>
+// ROWW (LEAN only, SHD_SCAN_ROW_WALK): an undecided candidate reads its exact
+// time from its row and walks in the scan, over positions whose times come
+// from the rows (RowPos), and a deferral leaves its resume position in
+// match_row.  Otherwise the lean scan reads no row and walks nothing: an
+// undecided candidate is deferred as it stands (no match_row entry: its walk
+// starts at p + 1) and k_resume_list replays the hot walk before the f2 walk.
+// That scan keeps the time table packed (earliest time as a 32-bit offset,
+// latest - earliest as a saturating 16-bit span; a saturated span decides
+// nothing, so the dead test stays a sufficient condition) and holds no walk
+// code: 8 workgroups per CU.
+template <bool LEAN, bool ROWW = false>
 __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __restrict__ ap, int64_t n_ext,
                                                              int64_t tile, const uint32_t* __restrict__ skey32,
                                                              const uint32_t* __restrict__ spv,
@@ -354,12 +364,20 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
   const int64_t tbase = a.x.batch.ts[0];
   const GlobalPos<false, false> ld{skey32, nullptr, spv, sts32, nullptr, tbase, a.partitioned};
   const RowPos ldr{skey32, spv, a.x.carry.ts, a.x.batch.ts, a.x.C, a.partitioned};
-  __shared__ int32_t ctab[LEAN ? 2 * kScanCoarse : 1];
+  constexpr bool PACKED = LEAN && !ROWW;
+  __shared__ int32_t ctab[LEAN ? (PACKED ? 1 : 2) * kScanCoarse : 1];
+  __shared__ uint16_t cspan[PACKED ? kScanCoarse : 1];
   if constexpr (LEAN) {
     const int nc = (int)((n_ext - 1) >> a.cbits) + 1;   // <= kScanCoarse
     for (int i = threadIdx.x; i < nc; i += kBlock) {
-      ctab[i] = a.ctab[i];
-      ctab[kScanCoarse + i] = a.ctab[kScanCoarse + i];
+      const int32_t lo = a.ctab[i], hi = a.ctab[kScanCoarse + i];
+      ctab[i] = lo;
+      if constexpr (PACKED) {
+        const int64_t sp = (int64_t)hi - (int64_t)lo;   // negative: an entry without a pushed row (never read)
+        cspan[i] = (uint16_t)(sp < 0 || sp > 0xFFFF ? 0xFFFF : sp);
+      } else {
+        ctab[kScanCoarse + i] = hi;
+      }
     }
     __syncthreads();
   }
@@ -416,18 +434,30 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
           } else {
             bool dead = false;
             if (kq == k && (fq & F_NEW) && !(fq & F_SKIP)) {
-              const int64_t hi = ri >= a.x.C ? tbase + ctab[kScanCoarse + (ri >> a.cbits)] : a.carry_tmax;
+              int64_t hi;
+              bool known = true;   // packed table: a saturated span leaves the candidate undecided
+              if (ri < a.x.C) {
+                hi = a.carry_tmax;
+              } else if constexpr (PACKED) {
+                const uint32_t sp = cspan[ri >> a.cbits];
+                known = sp != 0xFFFFu;
+                hi = tbase + ctab[ri >> a.cbits] + (int64_t)sp;
+              } else {
+                hi = tbase + ctab[kScanCoarse + (ri >> a.cbits)];
+              }
               const int64_t lo = tbase + ctab[rq >> a.cbits];
-              dead = lo > hi && (uint64_t)lo - (uint64_t)hi > (uint64_t)a.within;
+              dead = known && lo > hi && (uint64_t)lo - (uint64_t)hi > (uint64_t)a.within;
             }
             if (dead) {
               st = ST_DEAD;
               steps++;
-            } else {
+            } else if constexpr (ROWW) {
               tsi = ldr.row_ts(ri);
               tq = ldr.row_ts(rq);
               st = walk_partial<true, false, 1>(a, es, n_ext, ldr, ri, k, tsi, q, pq, tq, kq, tsi, false, j, steps,
                                                 viol, fm, ra, rb);
+            } else {
+              st = ST_DEFER;   // decided by k_resume_list, from p + 1
             }
           }
         } else {
@@ -436,7 +466,7 @@ __global__ __launch_bounds__(kBlock) void k_forward_scan_rec(const ScanArgs* __r
         }
         if (st == ST_DEFER) {
           out = PS_DEFER;
-          match_row[p] = (int32_t)q;   // resume position (< 2^28)
+          if constexpr (!PACKED) match_row[p] = (int32_t)q;   // resume position (< 2^28)
           nd++;
         } else if (st == ST_OPEN) {
           out = PS_OPEN;
@@ -988,7 +1018,13 @@ __global__ __launch_bounds__(kBlock) void k_forward_resume(const ScanArgs* __res
 // each thread searches for its sub-tile, and a walk that ends open adds to
 // its sub-tile's open count (sopen).
 // ROWT: the positions' times come from the rows (RowPos: lean key sort).
-template <bool K64, bool FAST, bool TS64, bool SUB = false, bool ROWT = false>
+// HOT (ROWT, the lean scan that reads no row): the scan deferred every
+// undecided candidate as it stood, so the walk starts at p + 1 with the
+// scan's own hot walk (no f2: it ends dead, open at the end of the key's run
+// -- the partial met no B event, so it stays in the new list: PS_OPEN without
+// PS_PEND -- or at the first B event inside `within`) and only then goes on
+// with f2 from that B event.
+template <bool K64, bool FAST, bool TS64, bool SUB = false, bool ROWT = false, bool HOT = false>
 __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restrict__ ap, int64_t n_ext, int64_t tile,
                                                         int ntile, const uint32_t* __restrict__ skey32,
                                                         const uint64_t* __restrict__ skey64,
@@ -1028,7 +1064,7 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
     } else {
       p = dlist[i];
     }
-    int64_t q = match_row[p];
+    int64_t q = HOT ? p + 1 : (int64_t)match_row[p];   // HOT: the scan deferred only where p + 1 < n_ext
     uint32_t pvp, pq;
     int64_t tsi, tq;
     uint64_t k = 0, kq = 0;
@@ -1038,8 +1074,16 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
     uint32_t fm = 0;
     int64_t ra = -1, rb = -1;
     if (a.logical == 2) and_carried(a, pv_row(pvp), fm, ra, rb);
-    const uint8_t st = walk_partial<false, FAST, 1, Ld, 0, false>(
-        a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tq, true, j, steps, viol, fm, ra, rb, p);
+    uint8_t st = ST_DEFER;
+    if constexpr (HOT) {
+      st = walk_partial<true, false, 1>(a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tsi, false, j, steps,
+                                        viol, fm, ra, rb);
+      if (st == ST_DEFER && q != p + 1) ld(q, pq, tq, kq);   // the B event the hot walk stopped at
+    }
+    const bool met_b = st == ST_DEFER;
+    if (met_b)
+      st = walk_partial<false, FAST, 1, Ld, 0, false>(a, es, n_ext, ld, pv_row(pvp), k, tsi, q, pq, tq, kq, tq, true, j,
+                                                      steps, viol, fm, ra, rb, p);
     uint8_t out = PS_NONE;
     const int t = (int)(p / tile);
     if (st == ST_MATCH) {
@@ -1048,7 +1092,8 @@ __global__ __launch_bounds__(kBlock) void k_resume_list(const ScanArgs* __restri
       if (a.logical == 2) match_other[p] = (int32_t)((j >> kRowBits) ? ra : rb);
       atomicAdd(&bcnt[t], 1u);
     } else if (st == ST_OPEN) {
-      out = PS_OPEN | PS_PEND;   // it met a B event of its key: in the pending list now
+      // a walk that met a B event of its key is in the pending list now
+      out = met_b ? (PS_OPEN | PS_PEND) : PS_OPEN;
       if (a.logical == 2) match_row[p] = and_code(fm, ra, rb);
       if (SUB) atomicAdd(&sopen[sti], 1u);
       else atomicAdd(&bcnt[ntile + t], 1u);
@@ -1261,7 +1306,11 @@ __device__ __forceinline__ void tile_compact(const uint8_t* __restrict__ pst, in
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_finish_scan(const ScanOut* blk, int nblk, ScanOut* out) {
+// ... and the time of the push's last event in arrival order (NeedNfa
+// hand-over: global expiry of unpartitioned plans), so that it arrives with
+// the totals' readback.
+__global__ __launch_bounds__(kBlock) void k_finish_scan(const ScanOut* blk, int nblk, ScanOut* out,
+                                                        const int64_t* ts_last, long long* t_last) {
   unsigned long long st = 0, pr = 0;
   uint32_t v = 0;
 #pragma unroll 8
@@ -1286,6 +1335,7 @@ __global__ __launch_bounds__(kBlock) void k_finish_scan(const ScanOut* blk, int 
       r.violation |= wpart[w].violation;
     }
     *out = r;
+    *t_last = (long long)*ts_last;
   }
 }
 
@@ -1871,6 +1921,8 @@ struct PatternEngine : Engine {
   DevBuf d_slice;   // lean key sort: the pushed rows' time range per row slice (keyed_sort_pass0)
   DevBuf d_ctab;    // ... folded to at most kScanCoarse entries (ScanArgs::ctab)
   hipEvent_t ev_pg = nullptr, ev_pt = nullptr;
+  hipEvent_t ev_scan = nullptr;   // the scan totals' readback (records path: the host waits on it, not on the stream)
+  const ProjArgs* d_proj = nullptr;   // k_project's arguments, staged with the carry gather's (gather_open)
   // sorted times of this push's positions (finish: carried partials' times)
   const int32_t* fin_sts32 = nullptr;
   const int64_t* fin_sts64 = nullptr;
@@ -2119,6 +2171,7 @@ struct PatternEngine : Engine {
   ~PatternEngine() override {
     if (ev_pg) (void)hipEventDestroy(ev_pg);
     if (ev_pt) (void)hipEventDestroy(ev_pt);
+    if (ev_scan) (void)hipEventDestroy(ev_scan);
   }
 
   void push(const Staged& b) override {
@@ -2188,8 +2241,6 @@ struct PatternEngine : Engine {
     ScanOut* d_so = &agg.dev()->scan;
     h_agg.prep = init;
     h_agg.scan = ScanOut{};
-    // the prepare and scan slots, up to the first scan total
-    SHD_HIP(hipMemcpyAsync(agg.dev(), &h_agg, offsetof(PatternTotals, n_match), hipMemcpyHostToDevice, s));
     // 4096 workgroups (16 waves per SIMD at full occupancy): enough to stream
     // at full bandwidth, and the one-block folds of the per-block partials
     // (k_finish_prep / k_finish_scan) stay short
@@ -2205,6 +2256,11 @@ struct PatternEngine : Engine {
     const bool fused = partitioned && !key64 && pa.key_col >= 0 && fattr >= -1 &&
                        (key_type[slot] == SHD_T_STRING || key_type[slot] == SHD_T_INT) && n_ext >= 2 &&
                        (fs_force >= 0 ? fs_force != 0 : n_ext >= ((int64_t)1 << 20));
+    // the prepare and scan slots, up to the first scan total.  The fused sort
+    // needs no identity on the device: k_ks_finish stores the whole prepare
+    // slot before k_ks_tfold merges into it, and k_finish_scan stores the scan slot
+    if (!fused)
+      SHD_HIP(hipMemcpyAsync(agg.dev(), &h_agg, offsetof(PatternTotals, n_match), hipMemcpyHostToDevice, s));
     KsInfo* d_ksi = &agg.dev()->ks;
     // lean key sort (the rows sorted without their time word; KsInfo::lean):
     // wherever the emitting scan can run as far as is known before the first
@@ -2471,17 +2527,21 @@ struct PatternEngine : Engine {
     // sorted times; any other path gets the sorted 32-bit offsets rebuilt from
     // the rows first (64-bit times were gathered above, k_sorted_ts64)
     const bool lean_scan = lean && slists && !prune && W != INT64_MAX;
+    // SHD_SCAN_ROW_WALK: the lean scan reads the rows of its undecided
+    // candidates and walks them itself; default: it defers them unread
+    const bool row_walk = knob_on(Knob::SCAN_ROW_WALK);
     if (lean && !lean_scan && !ts64) {
       d_ts.reserve(n_ext * 4);
       d_ts_alt.reserve(n_ext * 4);
       int32_t* ts_out = sorted_alt ? d_ts_alt.as<int32_t>() : d_ts.as<int32_t>();
-      hipLaunchKernelGGL(k_sorted_ts32, dim3(grid_cover(n_ext)), dim3(kBlock), 0, s, dev_args(x), spv, n_ext, ts_out);
+      // sa.x differs from x in the position-major columns only, which the times do not read
+      hipLaunchKernelGGL(k_sorted_ts32, dim3(grid_cover(n_ext)), dim3(kBlock), 0, s, &d_sa->x, spv, n_ext, ts_out);
       SHD_CHECK_LAUNCH();
       sts32 = ts_out;
     }
     if (lean_scan) {
       sts32 = nullptr;
-      hipLaunchKernelGGL(k_slice_coarsen, dim3(kScanCoarse / kBlock), dim3(kBlock), 0, s, dev_args(x),
+      hipLaunchKernelGGL(k_slice_coarsen, dim3(kScanCoarse / kBlock), dim3(kBlock), 0, s, &d_sa->x,
                          (const int64_t*)d_slice.as<int64_t>(), keyed_sort_slices(n_ext), sa.cbits, d_ctab.as<int32_t>());
       SHD_CHECK_LAUNCH();
     }
@@ -2549,12 +2609,15 @@ struct PatternEngine : Engine {
         fin_rec.pos = d_olist.as<uint32_t>();
         fin_rec.sub = tile / kSubPerTile;
         fin_rec.nsub = nsub;
+#define SHD_ARG(...) __VA_ARGS__
 #define SHD_LAUNCH_SCAN_REC(LEAN)                                                                                  \
-  hipLaunchKernelGGL(k_forward_scan_rec<LEAN>, dim3(ntile), dim3(kBlock), 0, s, d_sa, n_ext, tile, skey32, spv,    \
+  hipLaunchKernelGGL((k_forward_scan_rec<LEAN>), dim3(ntile), dim3(kBlock), 0, s, d_sa, n_ext, tile, skey32, spv,  \
                      sts32, d_match.as<int32_t>(), d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(),                     \
                      d_blk.as<ScanOut>(), fin_rec.key, fin_rec.pv, fin_rec.ts, fin_rec.pos, d_dlist.as<uint32_t>(), \
                      d_scnt)
-        if (lean_scan) SHD_LAUNCH_SCAN_REC(true); else SHD_LAUNCH_SCAN_REC(false);
+        if (lean_scan && row_walk) SHD_LAUNCH_SCAN_REC(SHD_ARG(true, true));
+        else if (lean_scan) SHD_LAUNCH_SCAN_REC(SHD_ARG(true, false));
+        else SHD_LAUNCH_SCAN_REC(false);
 #undef SHD_LAUNCH_SCAN_REC
       } else {
         if (ts64) SHD_LAUNCH_SCAN(false, true, false); else SHD_LAUNCH_SCAN(false, false, false);
@@ -2575,18 +2638,21 @@ struct PatternEngine : Engine {
         // then one lane per deferred walk
         uint32_t* d_ndef = &agg.dev()->n_deferred;
         scan_exclusive_u32(d_scnt + nsub, d_soff + nsub, nsub, d_ndef, d_scan, s);
-#define SHD_LAUNCH_RSUB(FAST, ROWT)                                                                                \
-  hipLaunchKernelGGL((k_resume_list<false, FAST, false, true, ROWT>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile, \
+#define SHD_LAUNCH_RSUB(FAST, ROWT, HOT)                                                                           \
+  hipLaunchKernelGGL((k_resume_list<false, FAST, false, true, ROWT, HOT>), dim3(nlb), dim3(kBlock), 0, s, d_sa, n_ext, tile, \
                      ntile, skey32, skey64, spv, sts32, sts64, d_match.as<int32_t>(), d_mother.as<int32_t>(),      \
                      d_pst.as<uint8_t>(), d_bcnt.as<uint32_t>(), d_blk.as<ScanOut>(), ntile,                       \
                      (const uint32_t*)d_dlist.as<uint32_t>(), (const uint32_t*)d_ndef,                             \
                      (const uint32_t*)(d_soff + nsub), nsub, fin_rec.sub, d_scnt)
-        if (lean_scan) {
-          if (fast2) SHD_LAUNCH_RSUB(true, true); else SHD_LAUNCH_RSUB(false, true);
+        if (lean_scan && !row_walk) {
+          if (fast2) SHD_LAUNCH_RSUB(true, true, true); else SHD_LAUNCH_RSUB(false, true, true);
+        } else if (lean_scan) {
+          if (fast2) SHD_LAUNCH_RSUB(true, true, false); else SHD_LAUNCH_RSUB(false, true, false);
         } else {
-          if (fast2) SHD_LAUNCH_RSUB(true, false); else SHD_LAUNCH_RSUB(false, false);
+          if (fast2) SHD_LAUNCH_RSUB(true, false, false); else SHD_LAUNCH_RSUB(false, false, false);
         }
 #undef SHD_LAUNCH_RSUB
+#undef SHD_ARG
       } else if (rlist) {
         // sparse keys: the deferred positions compacted into a list (per-tile
         // counts from k_forward_scan), then one lane per deferred walk
@@ -2622,7 +2688,7 @@ struct PatternEngine : Engine {
     // partials: [0, ntile) hot walk, [ntile, 2 ntile) deferred walks, [2 ntile, 3 ntile) continued walks
     hipLaunchKernelGGL(k_finish_scan, dim3(1), dim3(kBlock), 0, s, (const ScanOut*)d_blk.as<ScanOut>(),
                        rlist ? ntile + nlb : (rmode == 3 && !lockstep ? 3 : 2) * ntile,
-                       d_so);
+                       d_so, (const int64_t*)(b.cs.ts + (n - 1)), &agg.dev()->t_last);
     SHD_CHECK_LAUNCH();
     mark("forward_scan");
 
@@ -2634,10 +2700,25 @@ struct PatternEngine : Engine {
       scan_exclusive_u32(d_bcnt.as<uint32_t>() + ntile, d_boff.as<uint32_t>() + ntile, ntile, &agg.dev()->n_open,
                          d_scan, s);
     mark("compact");
-    agg.fetch(&PatternTotals::scan, &PatternTotals::tail_, s);
-    // time of the push's last event in arrival order (NeedNfa hand-over: global expiry of unpartitioned plans)
-    SHD_HIP(hipMemcpyAsync(&h_agg.t_last, b.cs.ts + (n - 1), 8, hipMemcpyDeviceToHost, s));
-    SHD_HIP(hipStreamSynchronize(s));
+    agg.fetch(&PatternTotals::scan, &PatternTotals::t_last, s);
+    fin_sts32 = sts32;
+    fin_sts64 = sts64;
+    if (fin_rec.on) {
+      // the scan's records: the carry gather needs nothing the host reads here
+      // (its grid is ntile, its offsets are on the device), so it is queued
+      // before the wait and runs while the host wakes up, sizes the match
+      // buffers and launches the match chain behind it.  Every open partial is
+      // a candidate among the extended rows: carry[nxt] is reserved for that
+      // bound.  A time regression still throws below: the gather has then
+      // written the uncommitted carry[nxt] only.
+      if (!ev_scan) SHD_HIP(hipEventCreateWithFlags(&ev_scan, hipEventDisableTiming));
+      SHD_HIP(hipEventRecord(ev_scan, s));
+      const int64_t bound = std::min<int64_t>(C + (int64_t)pg.n_cand, n_ext);
+      gather_open(b, x, n_ext, tile, ntile, spv, skey32, skey64, sorted64, keyed, grouped, key64, bound, true);
+      SHD_HIP(hipEventSynchronize(ev_scan));
+    } else {
+      SHD_HIP(hipStreamSynchronize(s));
+    }
     const ScanOut so = h_agg.scan;
     const uint32_t m = h_agg.n_match;
     const uint32_t n_open = h_agg.n_open;
@@ -2647,10 +2728,134 @@ struct PatternEngine : Engine {
       have_horizon = true;
       horizon = std::max(horizon, t_end);
     }
-    fin_sts32 = sts32;
-    fin_sts64 = sts64;
     finish(b, x, n_ext, tile, ntile, spv, skey32, skey64, sorted64, keyed, grouped, key64, m, n_open, so, t_end,
            pg.n_cand);
+  }
+
+  ProjArgs proj_args(const ExtRows& x) {
+    ProjArgs pr{};
+    pr.x = x;
+    pr.es = dset();
+    pr.nout = (int)outs.size();
+    pr.fast = 1;
+    for (size_t c = 0; c < outs.size(); c++) {
+      pr.outs[c] = dexpr(outs[c]);
+      if (!fast_atom(outs[c], pr.oat[c])) pr.fast = 0;
+    }
+    pr.multi = (sA == sB);
+    pr.logical = logical;
+    pr.s_first = s_first;
+    pr.s_second = s_second;
+    pr.se1 = d_se1.as<uint32_t>();
+    pr.sot = d_sot.as<int32_t>();
+    pr.chunk0 = chunk_seq;
+    pr.row0 = out.count;
+    return pr;
+  }
+
+  // The carry gather's side of the tail: carry[nxt] reserved for `rows` open
+  // partials, the gather's argument block staged and sent together with
+  // k_project's (one upload).  early (records path, before the host has read
+  // the push's totals: rows is an upper bound): the gather is launched here.
+  const GatherArgs* d_gather = nullptr;
+  const uint32_t* gather_k32 = nullptr;
+  const uint64_t* gather_k64 = nullptr;
+  void gather_open(const Staged& b, const ExtRows& x, int64_t n_ext, int64_t tile, int ntile, const uint32_t* spv,
+                   const uint32_t* skey32, const uint64_t* skey64, bool sorted64, bool keyed, bool grouped, bool key64,
+                   int64_t rows, bool early) {
+    const int nxt = cur ^ 1;
+    carry[nxt].reserve(rows, typesA);
+    d_gather = nullptr;
+    if (rows > 0) {
+      GatherArgs ga{};
+      ga.x = x;
+      ga.ncols = (int)typesA.size();
+      ga.partitioned = keyed;
+      ga.key64 = sorted64;
+      for (size_t c = 0; c < typesA.size(); c++) {
+        ga.types[c] = (int32_t)typesA[c];
+        ga.dcol[c] = carry[nxt].col[c].p;
+        ga.dnul[c] = carry[nxt].nul[c].as<uint8_t>();
+      }
+      ga.dts = carry[nxt].ts.as<int64_t>();
+      ga.dkey = carry[nxt].key.as<uint64_t>();
+      ga.dseq = carry[nxt].seq.as<int64_t>();
+      carry[cur].pend.reserve(std::max<int64_t>(C, 1));
+      ga.dpend = carry[nxt].pend.as<uint8_t>();
+      ga.pend_old = carry[cur].pend.as<uint8_t>();
+      if (logical == 2) {
+        carry[nxt].reserve_b(rows, typesB);
+        ga.and_mode = 1;
+        ga.match_row = d_match.as<int32_t>();
+        ga.dhalf = carry[nxt].half.as<uint8_t>();
+        ga.ncolsB = (int)typesB.size();
+        for (size_t c = 0; c < typesB.size(); c++) {
+          ga.typesB[c] = (int32_t)typesB[c];
+          ga.dcolB[c] = carry[nxt].bcol[c].p;
+          ga.dnulB[c] = carry[nxt].bnul[c].as<uint8_t>();
+        }
+        ga.dtsB = carry[nxt].bts.as<int64_t>();
+        ga.dseqB = carry[nxt].bseq.as<int64_t>();
+      }
+      if (keyed && !grouped) {   // positions are rows: the prepare output holds each row's key
+        ga.key64 = key64;
+        skey32 = d_k32.as<uint32_t>();
+        skey64 = d_k64.as<uint64_t>();
+      }
+      gather_k32 = skey32;
+      gather_k64 = skey64;
+      if (logical != 2) {
+        ga.amask = carry_mask;
+        if (grouped) {
+          ga.sts32 = fin_sts32;
+          ga.sts64 = fin_sts64;
+          // the partition key attribute of stream A, a 32-bit plain column (sorted key == its value)
+          ga.key_attr = (partitioned && !sorted64 && key_col[0] >= 0 &&
+                         (key_type[0] == SHD_T_STRING || key_type[0] == SHD_T_INT)) ? key_col[0] : -1;
+        } else {
+          ga.key_attr = -1;
+        }
+        if (!fin_rec.on) d_olist.reserve((size_t)rows * 4);
+      }
+      d_gather = args_stage(ga);
+    }
+    if (early) d_proj = gmembers.empty() ? args_stage(proj_args(x)) : nullptr;
+    args_send();
+    if (early && rows > 0) {
+      launch_gather(n_ext, tile, ntile, spv, skey32, skey64, rows);
+      mark("carry");
+    }
+  }
+
+  void launch_gather(int64_t n_ext, int64_t tile, int ntile, const uint32_t* spv, const uint32_t*, const uint64_t*,
+                     int64_t n_open) {
+    hipStream_t s = stream;
+    const uint32_t* skey32 = gather_k32;
+    const uint64_t* skey64 = gather_k64;
+    if (logical != 2) {
+      if (fin_rec.on) {
+#define SHD_LAUNCH_GATHER_REC(LEAN)                                                                               \
+  hipLaunchKernelGGL(k_gather_rec<LEAN>, dim3(ntile), dim3(kBlock), 0, s, d_gather, fin_rec.sub, fin_rec.nsub,     \
+                     (const uint32_t*)fin_rec.key, (const uint32_t*)fin_rec.pv, (const int32_t*)fin_rec.ts,        \
+                     (const uint32_t*)fin_rec.pos, (const uint32_t*)(d_bcnt.as<uint32_t>() + 3 * ntile),           \
+                     (const uint32_t*)(d_boff.as<uint32_t>() + 3 * ntile), (const uint8_t*)d_pst.as<uint8_t>())
+        if (fin_rec.lean) SHD_LAUNCH_GATHER_REC(true); else SHD_LAUNCH_GATHER_REC(false);
+#undef SHD_LAUNCH_GATHER_REC
+      } else {
+        hipLaunchKernelGGL(k_open_list, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),
+                           (const uint32_t*)d_boff.as<uint32_t>(), n_ext, tile, d_olist.as<uint32_t>(),
+                           (uint32_t)PS_OPEN, 1);
+        SHD_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_gather_list, dim3(grid_cover(n_open)), dim3(kBlock), 0, s, d_gather,
+                           (const uint32_t*)d_olist.as<uint32_t>(), n_open, (const uint8_t*)d_pst.as<uint8_t>(), spv,
+                           skey32, skey64);
+      }
+    } else {
+      hipLaunchKernelGGL(k_gather_carry, dim3(ntile), dim3(kBlock), 0, s, d_gather,
+                         (const uint8_t*)d_pst.as<uint8_t>(), (const uint32_t*)d_boff.as<uint32_t>(), spv, skey32,
+                         skey64, n_ext, tile);
+    }
+    SHD_CHECK_LAUNCH();
   }
 
   // Shared tail of a push: matches in (e2 event, creation) order -> projected
@@ -2660,7 +2865,8 @@ struct PatternEngine : Engine {
               uint32_t m, uint32_t n_open, const ScanOut& so, int64_t t_end, uint64_t n_cand) {
     hipStream_t s = stream;
     const int64_t n = b.n;
-    // ---- matches ordered by (e2 event, creation) -> projected output rows
+    // the records path queued the carry gather before the host wait (sort_push)
+    const bool gathered = fin_rec.on;
     if (m > 0) {
       d_pj.reserve((int64_t)m * 4);
       d_pi.reserve((int64_t)m * 4);
@@ -2670,6 +2876,15 @@ struct PatternEngine : Engine {
         d_se1.reserve((int64_t)m * 4);
         d_sot.reserve((int64_t)m * 4);
       }
+    }
+    // the tail's two argument blocks (k_project's, the carry gather's) in one upload
+    if (!gathered) {
+      d_proj = nullptr;
+      if (m > 0 && gmembers.empty()) d_proj = args_stage(proj_args(x));
+      gather_open(b, x, n_ext, tile, ntile, spv, skey32, skey64, sorted64, keyed, grouped, key64, n_open, false);
+    }
+    // ---- matches ordered by (e2 event, creation) -> projected output rows
+    if (m > 0) {
       hipLaunchKernelGGL(k_emit_pairs, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),
                          (const uint32_t*)d_boff.as<uint32_t>(), (const int32_t*)d_match.as<int32_t>(), spv, n_ext,
                          tile, logical, (const int32_t*)d_mother.as<int32_t>(), d_pj.as<uint32_t>(),
@@ -2690,24 +2905,7 @@ struct PatternEngine : Engine {
         mark("order_project");
       } else {
         out.ensure(m, s);
-        ProjArgs pr{};
-        pr.x = x;
-        pr.es = dset();
-        pr.nout = (int)outs.size();
-        pr.fast = 1;
-        for (size_t c = 0; c < outs.size(); c++) {
-          pr.outs[c] = dexpr(outs[c]);
-          if (!fast_atom(outs[c], pr.oat[c])) pr.fast = 0;
-        }
-        pr.multi = (sA == sB);
-        pr.logical = logical;
-        pr.s_first = s_first;
-        pr.s_second = s_second;
-        pr.se1 = d_se1.as<uint32_t>();
-        pr.sot = d_sot.as<int32_t>();
-        pr.chunk0 = chunk_seq;
-        pr.row0 = out.count;
-        hipLaunchKernelGGL(k_project, dim3(grid_cover(m)), dim3(kBlock), 0, s, dev_args(pr), pj, pi, (int64_t)m,
+        hipLaunchKernelGGL(k_project, dim3(grid_cover(m)), dim3(kBlock), 0, s, d_proj, pj, pi, (int64_t)m,
                            out.d_chunk(), out.d_type(), out.d_ts(), out.d_vals(), out.d_nulls(), out.d_seq(),
                            out.d_sidx());
         SHD_CHECK_LAUNCH();
@@ -2718,79 +2916,9 @@ struct PatternEngine : Engine {
     }
 
     // ---- carry the still-open partials
-    int nxt = cur ^ 1;
-    carry[nxt].reserve(n_open, typesA);
-    if (n_open > 0) {
-      GatherArgs ga{};
-      ga.x = x;
-      ga.ncols = (int)typesA.size();
-      ga.partitioned = keyed;
-      ga.key64 = sorted64;
-      for (size_t c = 0; c < typesA.size(); c++) {
-        ga.types[c] = (int32_t)typesA[c];
-        ga.dcol[c] = carry[nxt].col[c].p;
-        ga.dnul[c] = carry[nxt].nul[c].as<uint8_t>();
-      }
-      ga.dts = carry[nxt].ts.as<int64_t>();
-      ga.dkey = carry[nxt].key.as<uint64_t>();
-      ga.dseq = carry[nxt].seq.as<int64_t>();
-      carry[cur].pend.reserve(std::max<int64_t>(C, 1));
-      ga.dpend = carry[nxt].pend.as<uint8_t>();
-      ga.pend_old = carry[cur].pend.as<uint8_t>();
-      if (logical == 2) {
-        carry[nxt].reserve_b(n_open, typesB);
-        ga.and_mode = 1;
-        ga.match_row = d_match.as<int32_t>();
-        ga.dhalf = carry[nxt].half.as<uint8_t>();
-        ga.ncolsB = (int)typesB.size();
-        for (size_t c = 0; c < typesB.size(); c++) {
-          ga.typesB[c] = (int32_t)typesB[c];
-          ga.dcolB[c] = carry[nxt].bcol[c].p;
-          ga.dnulB[c] = carry[nxt].bnul[c].as<uint8_t>();
-        }
-        ga.dtsB = carry[nxt].bts.as<int64_t>();
-        ga.dseqB = carry[nxt].bseq.as<int64_t>();
-      }
-      if (keyed && !grouped) {   // positions are rows: the prepare output holds each row's key
-        ga.key64 = key64;
-        skey32 = d_k32.as<uint32_t>();
-        skey64 = d_k64.as<uint64_t>();
-      }
-      if (logical != 2) {
-        ga.amask = carry_mask;
-        if (grouped) {
-          ga.sts32 = fin_sts32;
-          ga.sts64 = fin_sts64;
-          // the partition key attribute of stream A, a 32-bit plain column (sorted key == its value)
-          ga.key_attr = (partitioned && !sorted64 && key_col[0] >= 0 &&
-                         (key_type[0] == SHD_T_STRING || key_type[0] == SHD_T_INT)) ? key_col[0] : -1;
-        } else {
-          ga.key_attr = -1;
-        }
-        if (fin_rec.on) {
-#define SHD_LAUNCH_GATHER_REC(LEAN)                                                                               \
-  hipLaunchKernelGGL(k_gather_rec<LEAN>, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga), fin_rec.sub, fin_rec.nsub, \
-                     (const uint32_t*)fin_rec.key, (const uint32_t*)fin_rec.pv, (const int32_t*)fin_rec.ts,        \
-                     (const uint32_t*)fin_rec.pos, (const uint32_t*)(d_bcnt.as<uint32_t>() + 3 * ntile),           \
-                     (const uint32_t*)(d_boff.as<uint32_t>() + 3 * ntile), (const uint8_t*)d_pst.as<uint8_t>())
-          if (fin_rec.lean) SHD_LAUNCH_GATHER_REC(true); else SHD_LAUNCH_GATHER_REC(false);
-#undef SHD_LAUNCH_GATHER_REC
-        } else {
-          d_olist.reserve((size_t)n_open * 4);
-          hipLaunchKernelGGL(k_open_list, dim3(ntile), dim3(kBlock), 0, s, (const uint8_t*)d_pst.as<uint8_t>(),
-                             (const uint32_t*)d_boff.as<uint32_t>(), n_ext, tile, d_olist.as<uint32_t>(),
-                             (uint32_t)PS_OPEN, 1);
-          SHD_CHECK_LAUNCH();
-          hipLaunchKernelGGL(k_gather_list, dim3(grid_cover((int64_t)n_open)), dim3(kBlock), 0, s, dev_args(ga),
-                             (const uint32_t*)d_olist.as<uint32_t>(), (int64_t)n_open,
-                             (const uint8_t*)d_pst.as<uint8_t>(), spv, skey32, skey64);
-        }
-      } else {
-        hipLaunchKernelGGL(k_gather_carry, dim3(ntile), dim3(kBlock), 0, s, dev_args(ga),
-                           (const uint8_t*)d_pst.as<uint8_t>(), (const uint32_t*)d_boff.as<uint32_t>(), spv, skey32,
-                           skey64, n_ext, tile);
-      }
-      SHD_CHECK_LAUNCH();
+    const int nxt = cur ^ 1;
+    if (!gathered && n_open > 0) {
+      launch_gather(n_ext, tile, ntile, spv, skey32, skey64, n_open);
       mark("carry");
     }
     SHD_HIP(hipEventRecord(ev1, s));

@@ -43,6 +43,7 @@ namespace shd {
   X(NO_IMPLICIT_KEY, "SHD_NO_IMPLICIT_KEY", FLAG, LOAD, "pattern: a key equality in f2 does not partition the plan")  \
   X(NO_LEAN_SORT, "SHD_NO_LEAN_SORT", FLAG, PUSH, "pattern: never the lean (two-word) key sort (wins over SHD_LEAN_SORT)") \
   X(LEAN_SORT, "SHD_LEAN_SORT", FLAG, PUSH, "pattern: the lean key sort wherever it can run, at any key density")     \
+  X(SCAN_ROW_WALK, "SHD_SCAN_ROW_WALK", FLAG, PUSH, "pattern: the lean scan walks its undecided candidates itself, from their rows") \
   /* keyed_sort.hip */                                                                                                \
   X(KS_GENERIC_F1, "SHD_KS_GENERIC_F1", FLAG, PUSH, "fused sort: f1 through eval_fpred per row, not pre-decoded")     \
   /* engine_nfa.hip */                                                                                                \

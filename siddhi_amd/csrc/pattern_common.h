@@ -388,7 +388,7 @@ enum : int { KS_LEAN_OFF = 0, KS_LEAN_AUTO = 1, KS_LEAN_ON = 2 };
 
 // The pattern engine's per-push readback block (PatternEngine::agg).  The
 // device layout is fixed: prepare and scan each own a 64-byte slot, and the
-// two compaction totals follow so that one copy from `scan` to `tail_`
+// two compaction totals and t_last follow so that one copy from `scan` to `t_last`
 // delivers everything the push reads after the forward scan.
 struct PatternTotals {
   PrepAgg prep;         // k_finish_prep, or keyed_sort_front + keyed_sort_pass0 (fused sort); host upload of the identity
@@ -396,20 +396,19 @@ struct PatternTotals {
   char scan_pad_[64 - sizeof(ScanOut)];   // rest of the scan slot (uploaded with it)
   uint32_t n_match;     // scan_exclusive_u32: completed matches
   uint32_t n_open;      // scan_exclusive_u32: partials still open
-  uint32_t tail_[2];    // unwritten; the last 8 bytes of the totals' readback
+  long long t_last;     // k_finish_scan: time of the push's last event in arrival order; ends the totals' readback
   char pad_[232 - 144];
   KsInfo ks;            // keyed_sort_front (fused sort)
   uint32_t n_deferred;  // scan_exclusive_u32: deferred walks of the resume list
 };
 static_assert(offsetof(PatternTotals, prep) == 0 && offsetof(PatternTotals, scan) == 64 &&
                   offsetof(PatternTotals, n_match) == 128 && offsetof(PatternTotals, n_open) == 132 &&
-                  offsetof(PatternTotals, tail_) + sizeof(uint32_t[2]) == 64 + 80 &&
+                  offsetof(PatternTotals, t_last) + sizeof(long long) == 64 + 80 &&
                   offsetof(PatternTotals, ks) == 232 && offsetof(PatternTotals, n_deferred) == 248 &&
                   sizeof(PatternTotals) <= 256,
               "PatternTotals device layout");
 // Host image: the device fields, then what only the host reads.
 struct PatternTotalsHost : PatternTotals {
-  int64_t t_last;        // time of the push's last event in arrival order (copied from the batch's ts column)
   PrepAgg prep_pass0;    // fused sort: `prep` again once keyed_sort_pass0 completed it
 };
 
