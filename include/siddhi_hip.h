@@ -99,7 +99,9 @@ typedef struct shd_out {
                                    processing emitted the row -- the completing
                                    event of a match, the last event of a group-by
                                    row, the first event of the call whose time
-                                   change fired a timer row.  Rows are in
+                                   change fired a timer row, the event whose call
+                                   produced a join row (for an EXPIRED trigger the
+                                   event that pushed it out).  Rows are in
                                    (in_seq, processor, pending-list) order, so the
                                    outputs of key-sharded queries merge by the
                                    global sequence of in_seq. */
@@ -107,7 +109,8 @@ typedef struct shd_out {
                                    processing emitted the row (the completing
                                    state of a pattern / sequence match, the
                                    absent state of a timer row); 0 for
-                                   single-stream (filter / window) queries   */
+                                   single-stream (filter / window) queries; the
+                                   trigger side's stream index for join rows  */
   /* list arena of SHD_T_OBJECT columns (multi-value selection of a count
      state without an index, `select e1.price` over `e1=S[..]<m:n>`: the
      reference's MultiValueVariableFunctionExecutor returns a java.util.List,
@@ -143,7 +146,7 @@ int shd_ctx_destroy(shd_ctx* ctx);
 int shd_plan_load(shd_ctx* ctx, const void* ir, size_t len, shd_query** out);
 int shd_plan_free(shd_query* q);
 /* Engine the plan runs on: 1 = pattern forward-scan, 2 = window/aggregate,
- * 3 = filter/projection, 4 = generic per-key NFA. */
+ * 3 = filter/projection, 4 = generic per-key NFA, 5 = stream-stream window join. */
 int shd_plan_engine(shd_query* q, int* engine);
 
 int shd_set_time(shd_query* q, int64_t ts);

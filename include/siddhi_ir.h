@@ -5,7 +5,7 @@
  *
  * A plan is a little-endian array of int32 words:
  *
- *   magic 'SHDP', version, kind (1 = STATE, 2 = SINGLE)
+ *   magic 'SHDP', version, kind (1 = STATE, 2 = SINGLE, 3 = JOIN)
  *   n_streams, { n_attrs, type[n_attrs] } * n_streams      (plan-local streams)
  *   n_consts,  { lo, hi } * n_consts                         (64-bit bit patterns)
  *   n_exprs,   { n_instr, { op, a, b, c } * n_instr } * n_exprs
@@ -13,6 +13,15 @@
  *   STATE:  state_type, within_lo, within_hi, n_states, node tree (prefix order)
  *   SINGLE: stream, n_handlers, { FILTER expr | WINDOW kind p_lo p_hi q_lo q_hi } * n_handlers
  *     (p = the window's first parameter, q = its second: see shd_window)
+ *   JOIN:   join_type (shd_join), then for the left and the right side
+ *             { stream, trigger, outer, wkind (0 = no window), p_lo, p_hi, n_filters, expr * n_filters },
+ *           then on_expr (-1 = absent: constant true)
+ *     (trigger: the side's CURRENT / EXPIRED events look the other side up -- 0 when the
+ *     other side is `unidirectional`; outer: a trigger of this side without a match emits
+ *     one row with the other side null.  Expressions address their operands by side:
+ *     LOAD / EVNULL / TS with a = 0 for the left side, 1 for the right; a side's filters
+ *     read only that side.  The selector of a JOIN plan has no aggregators, group-by or
+ *     having.  JoinInputStreamParser.java:200-225,334-452, JoinProcessor.java:107-190)
  *   selector: current_on, expired_on, n_aggs { kind, arg_expr, arg_type } ,
  *             n_group { expr }, having_expr, n_out { type, expr }
  *   optional trailing words:
@@ -45,7 +54,8 @@
 #define SHD_IR_VERSION 1
 #define SHD_IR_POST_MAGIC 0x54534F50 /* 'POST' */
 
-enum shd_kind { SHD_KIND_STATE = 1, SHD_KIND_SINGLE = 2 };
+enum shd_kind { SHD_KIND_STATE = 1, SHD_KIND_SINGLE = 2, SHD_KIND_JOIN = 3 };
+enum shd_join { SHD_JOIN_INNER = 0, SHD_JOIN_LEFT_OUTER = 1, SHD_JOIN_RIGHT_OUTER = 2, SHD_JOIN_FULL_OUTER = 3 };
 
 /* Attribute types (io.siddhi.query.api.definition.Attribute.Type). STRING is
  * a host dictionary id (u32); BOOL is a byte. */

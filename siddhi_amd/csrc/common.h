@@ -172,6 +172,15 @@ struct Plan {
   int single_stream = 0;
   struct Handler { int kind; int expr; int wkind; int64_t param, param2; };
   std::vector<Handler> handlers;
+  // JOIN plans: the left and the right side, the `on` expression (-1: absent)
+  struct JoinSide {
+    int stream = 0, trigger = 1, outer = 0, wkind = 0;
+    int64_t param = 0;
+    std::vector<int> filters;
+  };
+  int join_type = 0;
+  JoinSide jside[2];
+  int join_on = -1;
   bool current_on = true, expired_on = false;
   struct Agg { int kind, expr, type; };
   std::vector<Agg> aggs;

@@ -10,7 +10,7 @@
 
 namespace shd {
 
-enum EngineKind { ENG_PATTERN = 1, ENG_WINDOW = 2, ENG_FILTER = 3, ENG_NFA = 4 };
+enum EngineKind { ENG_PATTERN = 1, ENG_WINDOW = 2, ENG_FILTER = 3, ENG_NFA = 4, ENG_JOIN = 5 };
 
 // Device output arena: rows accumulate across pushes until polled.
 struct OutputBuffer {
@@ -315,6 +315,8 @@ std::unique_ptr<Engine> make_single_engine(const Plan& p, std::string& why);
 // keyed exact window engine: EXPIRED output, `having`, partitioned windows /
 // aggregates (engine_window.hip)
 std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why);
+// stream-stream window join (engine_join.hip)
+std::unique_ptr<Engine> make_join_engine(const Plan& p, std::string& why);
 std::unique_ptr<Engine> make_nfa_engine(const Plan& p, std::string& why);
 // list_hint: expected partials per key at once (sizes the per-key lists of an
 // unpartitioned plan; 0 = defaults)

@@ -132,6 +132,24 @@ Plan decode_plan(const int32_t* w, int64_t n) {
       }
       p.handlers.push_back(h);
     }
+  } else if (p.kind == SHD_KIND_JOIN) {
+    p.join_type = r.next();
+    if (p.join_type < SHD_JOIN_INNER || p.join_type > SHD_JOIN_FULL_OUTER)
+      throw Error(SHD_E_INVALID_PLAN, "bad join type");
+    for (int sd = 0; sd < 2; sd++) {
+      Plan::JoinSide& j = p.jside[sd];
+      j.stream = r.next();
+      j.trigger = r.next();
+      j.outer = r.next();
+      j.wkind = r.next();
+      j.param = r.next64();
+      const int nf = r.next();
+      if (nf < 0 || nf > 64) throw Error(SHD_E_INVALID_PLAN, "bad filter count");
+      for (int i = 0; i < nf; i++) j.filters.push_back(r.next());
+      if (j.stream < 0 || j.stream >= ns) throw Error(SHD_E_INVALID_PLAN, "bad join stream index");
+    }
+    p.join_on = r.next();
+    if (p.join_on < -1 || p.join_on >= ne) throw Error(SHD_E_INVALID_PLAN, "bad join condition");
   } else {
     throw Error(SHD_E_INVALID_PLAN, "bad plan kind");
   }
@@ -904,6 +922,8 @@ int shd_plan_load(shd_ctx* ctx, const void* ir, size_t len, shd_query** out) {
       if (!e && !knob_on(Knob::NO_ABSENT_SCAN) && !knob_on(Knob::FORCE_NFA)) e = make_absent_engine(p, why1);
       if (!e) e = make_nfa_engine(p, why2);
       if (!e) why1 += "; ";
+    } else if (p.kind == SHD_KIND_JOIN) {
+      e = make_join_engine(p, why2);
     } else {
       e = make_single_engine(p, why2);
     }

@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("SHD_LIB") or os.path.join(_HERE, "libsiddhi_hip.so")
 SHD_OK, SHD_E_INVALID_PLAN, SHD_E_UNSUPPORTED, SHD_E_OOM, SHD_E_DEVICE, SHD_E_CAPACITY, SHD_E_ARG = \
     0, -1, -2, -3, -4, -5, -6
 SHD_MEM_HOST, SHD_MEM_DEVICE = 0, 1
-ENGINE_NAMES = {1: "pattern-forward-scan", 2: "window-aggregate", 3: "filter-projection", 4: "nfa"}
+ENGINE_NAMES = {1: "pattern-forward-scan", 2: "window-aggregate", 3: "filter-projection", 4: "nfa", 5: "window-join"}
 
 EXPORTED = ["shd_device_count", "shd_ctx_create", "shd_ctx_destroy", "shd_plan_load", "shd_plan_free",
             "shd_plan_engine", "shd_set_time", "shd_push", "shd_flush", "shd_poll", "shd_discard_output",

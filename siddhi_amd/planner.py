@@ -27,7 +27,8 @@ from . import query_compiler as qc
 # ---- IR constants (mirror include/siddhi_ir.h) -----------------------------
 MAGIC, VERSION = 0x50444853, 1
 POST_MAGIC = 0x54534F50
-KIND_STATE, KIND_SINGLE = 1, 2
+KIND_STATE, KIND_SINGLE, KIND_JOIN = 1, 2, 3
+JOIN_TYPES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3}
 T_STRING, T_INT, T_LONG, T_FLOAT, T_DOUBLE, T_BOOL = 0, 1, 2, 3, 4, 5
 T_OBJECT = 6   # output only: a list over a count state's chain (include/siddhi_ir.h SHD_T_OBJECT)
 TYPE_CODE = {"string": T_STRING, "int": T_INT, "long": T_LONG, "float": T_FLOAT,
@@ -116,6 +117,10 @@ class Plan:
     # single
     single_stream: int = 0
     handlers: List[Tuple] = field(default_factory=list)
+    # join: type, [(stream, trigger, outer, window kind (0 = none), parameter, [filter exprs])] * 2, `on` (-1: absent)
+    join_type: int = 0
+    join_sides: List[Tuple] = field(default_factory=list)
+    join_on: int = -1
     # selector
     current_on: bool = True
     expired_on: bool = False
@@ -158,6 +163,11 @@ class Plan:
         if self.kind == KIND_STATE:
             w.extend([self.state_type, *_split64(self.within), self.n_states])
             w.extend(self.tree)
+        elif self.kind == KIND_JOIN:
+            w.append(self.join_type)
+            for stream, trigger, outer, wkind, param, fids in self.join_sides:
+                w.extend([stream, int(trigger), int(outer), wkind, *_split64(param), len(fids), *fids])
+            w.append(self.join_on)
         else:
             w.extend([self.single_stream, len(self.handlers)])
             for h in self.handlers:
@@ -517,6 +527,8 @@ def plan_query(app: qc.SiddhiApp, q: qc.Query, dictionary: StringDictionary,
         qp = _plan_state(app, q, dictionary, partition, extra_streams)
     elif isinstance(inp, qc.SingleInput):
         qp = _plan_single(app, q, dictionary, partition, extra_streams)
+    elif isinstance(inp, qc.JoinInput):
+        qp = _plan_join(app, q, dictionary, partition, extra_streams)
     else:
         raise UnsupportedPlanException("input kind %s is outside the hot path" % type(inp).__name__)
     if q.output_rate is not None:
@@ -819,6 +831,90 @@ def _plan_single(app, q, dictionary, partition, extra_streams) -> QueryPlan:
     plan.shape = {"kind": "single", "window": next((h[1] for h in plan.handlers if h[0] == H_WINDOW), 0)}
     return QueryPlan(plan, plan.to_bytes(), [si.stream], names, types, q.target, q.name,
                      partition is not None, {si.stream: "single"})
+
+
+def _plan_join(app, q, dictionary, partition, extra_streams) -> QueryPlan:
+    """A stream-stream window join (JoinInputStreamParser.parseInputStream,
+    C/util/parser/JoinInputStreamParser.java:88-352): each side is a defined
+    stream with filters and `length`, `time` or no window.  trigger: the side's
+    events look the other side up (both, or only the `unidirectional` one,
+    :200-225); outer: a trigger of that side without a match still emits a row
+    (:334-352: the left side of `left outer`, the right of `right outer`, both
+    of `full outer`).  Expressions address operands by side (state 0 = left,
+    1 = right); an unqualified attribute found on both sides and a side named
+    by its stream id when it has an alias fail validation as in the reference
+    (ExpressionParser.parseVariable)."""
+    ji: qc.JoinInput = q.input
+    if partition is not None:
+        raise UnsupportedPlanException("joins inside a partition are outside the hot path")
+    if ji.within is not None or ji.per is not None:
+        raise UnsupportedPlanException("join `within` / `per` (aggregation joins) is outside the hot path")
+    if q.output_rate is not None:
+        raise UnsupportedPlanException("output rate limiting on a join query is outside the hot path")
+    sel = q.selector
+    if sel.group_by:
+        raise UnsupportedPlanException("group by over a join is outside the hot path")
+    if sel.having is not None:
+        raise UnsupportedPlanException("having over a join is outside the hot path")
+    if any(_has_agg(oa.expr) for oa in sel.attrs):
+        raise UnsupportedPlanException("aggregating selectors over a join are outside the hot path")
+    sides = (ji.left, ji.right)
+    for s in sides:
+        if s.inner or s.stream.startswith("#"):
+            raise UnsupportedPlanException("partition-inner streams (#stream) are outside the hot path")
+        if s.stream not in app.streams and s.stream not in (extra_streams or {}):
+            raise UnsupportedPlanException("join side '%s' is not a defined stream: tables, named windows and "
+                                           "aggregations are outside the hot path" % s.stream)
+    if ji.left.stream == ji.right.stream:
+        raise UnsupportedPlanException("self-joins (both sides the same stream) are outside the hot path")
+    metas = [_stream_meta(app, s.stream, s.ref, extra_streams) for s in sides]
+    streams = [s.stream for s in sides]
+    plan = Plan(KIND_JOIN, q.name, streams, [[t for _, t in m.attrs] for m in metas])
+    plan.join_type = JOIN_TYPES[ji.type]
+    ec = ExprCompiler(plan, dictionary, metas, state_query=True)
+    uni = (ji.left_unidirectional, ji.right_unidirectional)
+    if uni[0] and uni[1]:
+        raise SiddhiAppValidationException("Both sides of a join cannot be unidirectional")
+    outer = (ji.type in ("left_outer", "full_outer"), ji.type in ("right_outer", "full_outer"))
+    refused = None
+    for i, s in enumerate(sides):
+        fids, wkind, param, n_windows = [], 0, 0, 0
+        for h in s.handlers:
+            if isinstance(h, qc.Filter):
+                if n_windows:
+                    raise UnsupportedPlanException("a filter after the window of a join side is outside the hot path")
+                eid, _ = ec.compile(h.expr, i, IDX_CURRENT, want_bool=True)
+                fids.append(eid)
+                continue
+            n_windows += 1
+            if n_windows > 1:
+                raise SiddhiAppValidationException("only one window per stream")
+            if h.name == "time":
+                # refused below, once the query has passed the reference's own validation
+                refused = "time windows on a join side are outside the hot path"
+                continue
+            if h.name != "length":
+                raise UnsupportedPlanException("window %s on a join side is outside the hot path (length or none)"
+                                               % h.name)
+            _, wkind, param, _ = _window_handler(h, False)
+            if param <= 0:
+                raise UnsupportedPlanException("length(0) on a join side is outside the hot path")
+        plan.join_sides.append((i, not uni[1 - i], outer[i], wkind, param, fids))
+    if ji.on is not None:
+        plan.join_on, _ = ec.compile(ji.on, UNKNOWN_STATE, 0, want_bool=True)
+    if sel.select_all:
+        both = [n for n, _ in metas[0].attrs if metas[1].attr(n) is not None]
+        if both:
+            # `select *` names every attribute of both sides in one output definition
+            raise SiddhiAppValidationException("'%s' is already defined for the output of the join" % both[0])
+    names, types = _plan_selector(plan, q, ec, metas, True)
+    if refused is not None:
+        raise UnsupportedPlanException(refused)
+    plan.target = q.target
+    plan.states = metas
+    plan.shape = {"kind": "join", "type": ji.type}
+    return QueryPlan(plan, plan.to_bytes(), streams, names, types, q.target, q.name, False,
+                     {s: "single" for s in streams})
 
 
 def _window_handler(h, partitioned: bool, meta=None, stream=None, plan=None):

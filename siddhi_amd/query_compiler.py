@@ -7,6 +7,8 @@ SiddhiQL.g4`):
 * `define stream` (g4 `definition_stream`),
 * annotations `@app:playback`, `@app:name`, `@info(name=...)`,
 * single-stream queries with filters and `#window.length/time` (g4 :190-192),
+* joins of two such streams, `A#window... [unidirectional] [left|right|full outer |
+  inner] join B#window... [unidirectional] [on <condition>]` (g4 join_stream),
 * pattern (`->`) and sequence (`,`) inputs with `every`, `within`, count
   `<m:n>` / `* ? +`, logical `and`/`or`, absent `not X for t` (g4 :200-335),
 * select / group by / having / insert [current|expired|all events] into
@@ -109,6 +111,20 @@ class SingleInput:
     handlers: list                   # [Filter|Window] in textual order
     ref: Optional[str] = None
     inner: bool = False
+
+
+@dataclass
+class JoinInput:
+    """`<left> [unidirectional] <join type> <right> [unidirectional] [on <condition>]`
+    (g4 join_stream; query-api JoinInputStream)."""
+    left: SingleInput
+    right: SingleInput
+    type: str                          # 'inner' | 'left_outer' | 'right_outer' | 'full_outer'
+    on: object = None
+    left_unidirectional: bool = False
+    right_unidirectional: bool = False
+    within: object = None              # aggregation joins only: `within ... per ...`
+    per: object = None
 
 
 @dataclass
@@ -484,7 +500,7 @@ class Parser:
         # Decide between standard stream, pattern and sequence by scanning to the
         # end of the input section (select / insert at depth 0).
         depth, j = 0, self.i
-        saw_arrow = saw_comma = saw_every = saw_eq = saw_not = False
+        saw_arrow = saw_comma = saw_every = saw_eq = saw_not = saw_join = False
         while True:
             t = self.toks[j]
             if t.kind == "eof":
@@ -506,8 +522,10 @@ class Parser:
             elif depth == 0 and t.text == "=" and self.toks[j - 1].kind == "id":
                 saw_eq = True
             elif depth == 0 and t.kind == "id" and t.low in ("join", "unidirectional"):
-                raise OutOfScopeSyntax("joins are outside the hot path")
+                saw_join = True
             j += 1
+        if saw_join:
+            return self.join_stream()
         if saw_arrow or (saw_every and not saw_comma) or (saw_not and not saw_comma) or (saw_eq and not saw_comma):
             el = self.pattern_chain()
             within = self.within()
@@ -517,6 +535,37 @@ class Parser:
             within = self.within()
             return StateInput("sequence", el, within)
         return self.standard_stream()
+
+    def join_stream(self) -> JoinInput:
+        left = self.standard_stream()
+        left_uni = self.accept("unidirectional")
+        if self.accept("left"):
+            self.expect("outer")
+            kind = "left_outer"
+        elif self.accept("right"):
+            self.expect("outer")
+            kind = "right_outer"
+        elif self.accept("full"):
+            self.expect("outer")
+            kind = "full_outer"
+        else:
+            self.accept("inner")
+            kind = "inner"
+        self.expect("join")
+        right = self.standard_stream()
+        right_uni = self.accept("unidirectional")
+        on = None
+        if self.accept("on"):
+            on = self.expression()
+        within = per = None
+        if self.accept("within"):
+            # an aggregation join's `within <start>[, <end>] per <granularity>`
+            within = self.expression()
+            if self.accept(","):
+                self.expression()
+        if self.accept("per"):
+            per = self.expression()
+        return JoinInput(left, right, kind, on, left_uni, right_uni, within, per)
 
     def within(self):
         if self.accept("within"):
