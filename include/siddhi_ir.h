@@ -16,7 +16,10 @@
  *   JOIN:   join_type (shd_join), then for the left and the right side
  *             { stream, trigger, outer, wkind (0 = no window), p_lo, p_hi, n_filters, expr * n_filters },
  *           then on_expr (-1 = absent: constant true)
- *     (trigger: the side's CURRENT / EXPIRED events look the other side up -- 0 when the
+ *     (wkind: 0, SHD_W_LENGTH with p = the length, or SHD_W_EXTERNAL_TIME with p packed as
+ *     SHD_JOIN_EXT_*: bits 0-47 the window time T (0 < T < 2^48), bits 48-63 the side's LONG
+ *     attribute holding the event time -- ExternalTimeWindowProcessor.java:125-186.
+ *     trigger: the side's CURRENT / EXPIRED events look the other side up -- 0 when the
  *     other side is `unidirectional`; outer: a trigger of this side without a match emits
  *     one row with the other side null.  Expressions address their operands by side:
  *     LOAD / EVNULL / TS with a = 0 for the left side, 1 for the right; a side's filters
@@ -141,6 +144,9 @@ enum shd_etb_start { SHD_ETB_START_NONE = 0, SHD_ETB_START_CONST = 1, SHD_ETB_ST
 #define SHD_ETB_START_MODE(q) ((int)(((q) >> 16) & 3))
 #define SHD_ETB_REPLACE(q) ((int)(((q) >> 18) & 1))
 #define SHD_ETB_START_REF(q) ((int)(((q) >> 24) & 0xFFFF))
+/* The p word of an externalTime side of a JOIN plan. */
+#define SHD_JOIN_EXT_TIME(p) ((long long)((unsigned long long)(p) & 0xFFFFFFFFFFFFull))
+#define SHD_JOIN_EXT_TS_COL(p) ((int)(((unsigned long long)(p) >> 48) & 0xFFFF))
 enum shd_agg { SHD_AGG_SUM = 1, SHD_AGG_AVG = 2, SHD_AGG_COUNT = 3 };
 
 /* Output / input event types (ComplexEvent.Type). */

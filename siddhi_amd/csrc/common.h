@@ -175,7 +175,8 @@ struct Plan {
   // JOIN plans: the left and the right side, the `on` expression (-1: absent)
   struct JoinSide {
     int stream = 0, trigger = 1, outer = 0, wkind = 0;
-    int64_t param = 0;
+    int64_t param = 0;   // length: L; externalTime: T
+    int ts_col = -1;     // externalTime: the LONG attribute holding the event time
     std::vector<int> filters;
   };
   int join_type = 0;
@@ -250,6 +251,8 @@ __host__ __device__ __forceinline__ uint32_t key_bucket_mix(uint32_t k) {
 // Exclusive scan of u32 counts -> u32 offsets; returns nothing (total read from out[n-1]+in[n-1]).
 void scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* total_dev,
                         DevBuf& scratch, hipStream_t s);
+// Inclusive running maximum of i64: out[i] = max(in[0 .. i]); in and out do not overlap.
+void scan_inclusive_max_i64(const int64_t* in, int64_t* out, int64_t n, DevBuf& scratch, hipStream_t s);
 // Stable LSD radix sort of (key, value) pairs over key bits [0, bits).
 void radix_sort_pairs_u32(uint32_t* keys, uint32_t* vals, uint32_t* keys_alt, uint32_t* vals_alt,
                           int64_t n, int bits, DevBuf& scratch, hipStream_t s, bool& result_in_alt);

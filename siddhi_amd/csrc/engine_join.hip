@@ -5,6 +5,7 @@
 //   util/parser/JoinInputStreamParser.java:200-225,334-352,393-452 (sides, trigger / outer flags)
 //   query/processor/stream/window/LengthWindowProcessor.java:105-158 (chunk order, find on the queue)
 //   query/processor/stream/window/EmptyWindowProcessor.java:66-120 (a side without a window)
+//   query/processor/stream/window/ExternalTimeWindowProcessor.java:125-161,174-186 (event-time side)
 //   util/parser/OperatorParser.java (constructOperator over an event queue: matches oldest first)
 //   query/selector/QuerySelector.java process(List<ComplexEventChunk>) (type filter, one output chunk)
 //
@@ -13,9 +14,10 @@
 // a contiguous range of that sequence, so a trigger event of side X meets the
 // items [lo, hi) of side Y, where the range depends only on the trigger's call.
 // One push of X appends X's items, enumerates its trigger slots in chunk order
-// (closed form: no trigger list is built), counts each slot's matches
-// (k_join_count), scans the counts into row offsets and writes the rows
-// (k_join_emit, the same walk).  Both kernels are a nested-loop band join: a
+// (closed form for `length` and windowless sides; an externalTime side, whose
+// events expire a variable number of items, builds a trigger list first: see
+// "externalTime sides" below), counts each slot's matches (k_join_count), scans
+// the counts into row offsets and writes the rows (k_join_emit, the same walk).  Both kernels are a nested-loop band join: a
 // workgroup owns kJoinTrig consecutive slots, one per thread, and walks the
 // union of their Y ranges in tiles of kJoinTile items staged in LDS; every
 // lane reads the same staged item at the same time (LDS broadcast reads).
@@ -58,6 +60,10 @@ struct JoinArgs {
   int32_t self_exp;    // no window: an item's EXPIRED event follows its own CURRENT one
   int32_t outer;       // a slot without a match emits one row with Y null
   int64_t C, L, nslots;
+  int32_t ext;               // X is an externalTime side: the slots are the records of its trigger list
+  const int32_t* trig_item;  // [nslots] the X item the slot's event carries
+  const int32_t* trig_by;    // [nslots] the new item whose arrival made the event (itself: CURRENT)
+  const int64_t* xtau;       // X's time attribute, per item (stamp of its EXPIRED events)
   const int64_t* call_now;   // [ncalls] the clock of each call (stamp of EXPIRED events)
   // Y: the side that is looked up
   const uint64_t* yattr;   // [yncols][ycap]
@@ -81,6 +87,16 @@ struct Trig {
 
 __device__ __forceinline__ Trig join_slot(const JoinArgs& a, int64_t u) {
   Trig t;
+  if (a.ext) {
+    const int64_t fresh = a.C + gld(a.trig_by, u);
+    t.item = gld(a.trig_item, u);
+    t.call = gld(a.xcall, fresh);
+    t.seq = gld(a.xseq, fresh);
+    t.valid = true;
+    t.type = t.item == fresh ? SHD_EV_CURRENT : SHD_EV_EXPIRED;
+    t.ts = t.type == SHD_EV_CURRENT ? gld(a.xts, fresh) : gld(a.xtau, fresh);
+    return t;
+  }
   const int64_t j = u / a.per;
   const int k = (int)(u - j * a.per);
   const int64_t fresh = a.C + j;
@@ -206,9 +222,77 @@ struct JoinTotals {
   uint32_t scan_total;   // scan_exclusive_u32 over the slots' row counts
   uint32_t pad;
   uint64_t rows;         // the same total in 64 bits (k_join_total): the capacity check
+  int64_t lo_last;       // externalTime side: first item of its window after the push (k_jext_lo)
 };
-static_assert(offsetof(JoinTotals, scan_total) == 0 && offsetof(JoinTotals, rows) == 8 && sizeof(JoinTotals) <= 64,
+static_assert(offsetof(JoinTotals, scan_total) == 0 && offsetof(JoinTotals, rows) == 8 &&
+                  offsetof(JoinTotals, lo_last) == 16 && sizeof(JoinTotals) <= 64,
               "JoinTotals device layout");
+
+// ---------------------------------------------------------------- externalTime sides
+// ExternalTimeWindowProcessor pops its queue's head while tau_head - tau_j + T
+// <= 0 when item j arrives, and stops at the first head that is not due.  With
+// M the running maximum of tau over the side's items (scan_inclusive_max_i64),
+// the window after item j is [lo_j, j], lo_j the first i with M_i - M_j + T > 0
+// (M never decreases: a binary search), and item j expires [lo_{j-1}, lo_j).
+// The carried items are the window itself, so lo_{-1} = 0 and the maximum over
+// carried + new items is the maximum over all history.  In chunk order the
+// events before item j's group are lo_{j-1} EXPIRED and j CURRENT ones, which
+// places every wanted event without a scan: expired item e lands at
+// e + (CURRENT wanted ? j : 0) for its expirer j (the first j with lo_j > e),
+// item j's CURRENT event at (EXPIRED wanted ? lo_j : 0) + j.
+struct JoinExtArgs {
+  const int64_t* M;      // [C + m] running maximum of the time attribute
+  int64_t C, m, T;
+  int64_t* lo;           // [m] first item of the window after new item j
+  int64_t nexp;          // EXPIRED slots of the push (0 when the output does not want them)
+  int32_t want_cur;
+  int32_t* trig_item;    // [nexp + (want_cur ? m : 0)]
+  int32_t* trig_by;
+  JoinTotals* tot;
+};
+
+__global__ __launch_bounds__(kBlock) void k_jext_lo(const JoinExtArgs* __restrict__ ap) {
+  const JoinExtArgs& a = *ap;
+  for (int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x; j < a.m; j = a.m) {
+    const int64_t g = a.C + j;
+    const int64_t mg = gld(a.M, g);
+    int64_t l = 0, h = g;   // M_g - M_g + T > 0: the answer is in [0, g]
+    while (l < h) {
+      const int64_t mid = l + ((h - l) >> 1);
+      if (gld(a.M, mid) - mg + a.T > 0) h = mid;
+      else l = mid + 1;
+    }
+    a.lo[j] = l;
+    if (j == a.m - 1) a.tot->lo_last = l;
+  }
+}
+
+// One thread per wanted event of the push: the expired items [0, nexp), then
+// the new items.
+__global__ __launch_bounds__(kBlock) void k_jext_trig(const JoinExtArgs* __restrict__ ap) {
+  const JoinExtArgs& a = *ap;
+  const int64_t n = a.nexp + (a.want_cur ? a.m : 0);
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i = n) {
+    int64_t slot, item, by;
+    if (i < a.nexp) {   // its expirer: the first new item j with lo_j > i (lo_{m-1} >= nexp > i)
+      int64_t l = 0, h = a.m - 1;
+      while (l < h) {
+        const int64_t mid = l + ((h - l) >> 1);
+        if (gld(a.lo, mid) > i) h = mid;
+        else l = mid + 1;
+      }
+      by = l;
+      item = i;
+      slot = i + (a.want_cur ? by : 0);
+    } else {
+      by = i - a.nexp;
+      item = a.C + by;
+      slot = (a.nexp > 0 ? gld(a.lo, by) : 0) + by;
+    }
+    a.trig_item[slot] = (int32_t)item;
+    a.trig_by[slot] = (int32_t)by;
+  }
+}
 
 // cnt[u] = rows of slot u: its matches, or 1 for an outer slot without one;
 // blk[b] = rows of workgroup b's slots (folded by k_join_total: no atomics on
@@ -309,7 +393,9 @@ struct JoinEngine : Engine {
   struct Side {
     int stream = 0, wkind = 0, ncols = 0;
     bool trigger = true, outer = false;
-    int64_t L = 0;
+    int64_t L = 0;   // length: L; externalTime: T
+    int tcol = -1;   // externalTime: the attribute holding the event time
+    bool ext() const { return wkind == SHD_W_EXTERNAL_TIME; }
     std::vector<int> filters;
     ItemStore items;
     int64_t C = 0;   // items held: [0, C) of slot items.cur, in arrival order
@@ -319,6 +405,7 @@ struct JoinEngine : Engine {
 
   DevBuf d_offs, d_call_of, d_last, d_call_now, d_ylo;
   DevBuf d_flags, d_cnt, d_off, d_pkey, d_rows, d_roff, d_blk, d_scan;
+  DevBuf d_M, d_lo, d_trig_item, d_trig_by;   // externalTime sides
   PinnedBuf h_pin;
   ReadbackBlock<JoinTotals> tot;
 
@@ -400,6 +487,7 @@ struct JoinEngine : Engine {
     xa.ncols = X.ncols;
     xa.C = X.C;
     xa.seq0 = seq;
+    xa.notnull1 = X.ext() ? X.tcol + 1 : 0;   // a null event time: the event does not enter the join
     tot.reserve();
     launch(k_xw_filter, n, dev_args(xa), n, d_flags.as<uint8_t>(), d_cnt.as<uint32_t>(), d_pkey.as<uint64_t>());
     const int64_t m = scan(d_cnt.as<uint32_t>(), d_off.as<uint32_t>(), n, &tot.dev()->scan_total,
@@ -416,12 +504,44 @@ struct JoinEngine : Engine {
     }
     mark("items");
 
+    // externalTime: the running maximum of X's time attribute, the window's
+    // first item after each new item, and the item the push's window starts at
+    int64_t lo_last = 0;
+    JoinExtArgs ea{};
+    if (X.ext() && m > 0) {
+      d_M.reserve((size_t)total * 8);
+      d_lo.reserve((size_t)m * 8);
+      const int64_t* tau = reinterpret_cast<const int64_t*>(xp.attr) + (int64_t)X.tcol * xa.cap;
+      scan_inclusive_max_i64(tau, d_M.as<int64_t>(), total, d_scan, stream);
+      ea.M = d_M.as<int64_t>();
+      ea.C = X.C;
+      ea.m = m;
+      ea.T = X.L;
+      ea.lo = d_lo.as<int64_t>();
+      ea.tot = tot.dev();
+      launch(k_jext_lo, m, dev_args(ea));
+      tot.fetch(&JoinTotals::lo_last, stream);
+      SHD_HIP(hipStreamSynchronize(stream));
+      lo_last = tot.host().lo_last;
+      mark("window");
+    }
+
     // trigger slots, their matches and rows
     const int per = (plan.current_on ? 1 : 0) + (plan.expired_on ? 1 : 0);
     int64_t nrows = 0, nslots = 0;
-    if (X.trigger && m > 0 && per > 0) {
-      nslots = m * per;
+    if (X.trigger && m > 0)
+      nslots = X.ext() ? (plan.expired_on ? lo_last : 0) + (plan.current_on ? m : 0) : m * per;
+    if (nslots > 0) {
       if (nslots >= (int64_t)INT32_MAX) throw Error(SHD_E_CAPACITY, "join triggers exceed 2^31");
+      if (X.ext()) {   // the trigger list, in chunk order
+        d_trig_item.reserve((size_t)nslots * 4);
+        d_trig_by.reserve((size_t)nslots * 4);
+        ea.nexp = plan.expired_on ? lo_last : 0;
+        ea.want_cur = plan.current_on;
+        ea.trig_item = d_trig_item.as<int32_t>();
+        ea.trig_by = d_trig_by.as<int32_t>();
+        launch(k_jext_trig, nslots, dev_args(ea));
+      }
       // Y's window at each call: the items it holds (length and windowless
       // sides keep exactly their window between pushes)
       upload(d_call_now, call_now);
@@ -459,6 +579,12 @@ struct JoinEngine : Engine {
       ja.C = X.C;
       ja.L = X.L;
       ja.nslots = nslots;
+      ja.ext = X.ext();
+      if (ja.ext) {
+        ja.trig_item = d_trig_item.as<int32_t>();
+        ja.trig_by = d_trig_by.as<int32_t>();
+        ja.xtau = reinterpret_cast<const int64_t*>(xp.attr) + (int64_t)X.tcol * xa.cap;
+      }
       ja.call_now = d_call_now.as<int64_t>();
       const ItemPtrs yp = Y.items.ptrs(Y.items.cur);
       ja.yattr = yp.attr;
@@ -492,8 +618,9 @@ struct JoinEngine : Engine {
       mark("join_emit");
     }
 
-    // carry: X keeps its window (length: the last L items; no window: nothing)
-    const int64_t kept = X.wkind == SHD_W_LENGTH ? std::min<int64_t>(X.L, total) : 0;
+    // carry: X keeps its window (length: the last L items; externalTime: the
+    // items from lo_last on, however many; no window: nothing)
+    const int64_t kept = X.ext() ? total - lo_last : X.wkind == SHD_W_LENGTH ? std::min<int64_t>(X.L, total) : 0;
     const int64_t from = total - kept;
     if (kept > 0 && from > 0) {
       ItemStore& it = X.items;
@@ -537,7 +664,9 @@ struct JoinEngine : Engine {
   void load_state(SnapR& r) override {
     for (Side& s : side) {
       const int64_t c0 = r.get<int64_t>();
-      if (r.get<int32_t>() != s.ncols || c0 < 0 || (s.wkind == SHD_W_LENGTH ? c0 > s.L : c0 > 0))
+      // an externalTime window holds any number of items
+      const int64_t most = s.ext() ? (int64_t)INT32_MAX - 1 : s.wkind == SHD_W_LENGTH ? s.L : 0;
+      if (r.get<int32_t>() != s.ncols || c0 < 0 || c0 > most)
         throw Error(SHD_E_ARG, "snapshot of a different plan");
       s.items.cur = 0;
       if (c0 > 0) {
@@ -565,7 +694,17 @@ std::unique_ptr<Engine> make_join_engine(const Plan& p, std::string& why) {
     const auto& types = p.stream_types[j.stream];
     if (types.size() > (size_t)kMaxCols) { why = "too many attributes"; return nullptr; }
     if (j.filters.size() > 4) { why = "too many filters"; return nullptr; }
-    if (j.wkind != 0 && j.wkind != SHD_W_LENGTH) { why = "join side window other than length"; return nullptr; }
+    if (j.wkind != 0 && j.wkind != SHD_W_LENGTH && j.wkind != SHD_W_EXTERNAL_TIME) {
+      why = "join side window other than length or externalTime";
+      return nullptr;
+    }
+    // externalTime: shd_api.cpp has split the packed word into T (param) and the time attribute (ts_col)
+    if (j.wkind == SHD_W_EXTERNAL_TIME &&
+        (j.param <= 0 || j.param >= (int64_t(1) << 48) || j.ts_col < 0 || j.ts_col >= (int)types.size() ||
+         types[j.ts_col] != SHD_T_LONG)) {
+      why = "externalTime join side: window time outside (0, 2^48) or no LONG time attribute";
+      return nullptr;
+    }
     if (j.wkind == SHD_W_LENGTH && (j.param <= 0 || j.param >= (int64_t)INT32_MAX)) {
       why = "length window of 0 or beyond 2^31 on a join side";
       return nullptr;
@@ -573,6 +712,7 @@ std::unique_ptr<Engine> make_join_engine(const Plan& p, std::string& why) {
     s.stream = j.stream;
     s.wkind = j.wkind;
     s.L = j.param;
+    s.tcol = j.ts_col;
     s.trigger = j.trigger != 0;
     s.outer = j.outer != 0;
     s.filters = j.filters;

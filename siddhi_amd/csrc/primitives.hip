@@ -120,6 +120,101 @@ void scan_exclusive_u32(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* 
   scan_raw(in, out, n, total_dev, scratch.as<uint32_t>(), s);
 }
 
+// ============================================================ running maximum
+// Inclusive max-scan of i64, in the shape of the scan above: every workgroup
+// reduces its tile, the tile maxima are scanned recursively, and a down-sweep
+// combines each element's in-tile prefix with the maximum of the tiles before
+// it.  Workgroups never wait on one another and share no atomic counter.
+__device__ inline int64_t wave_incl_max(int64_t v) {
+  int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    int64_t t = __shfl_up((long long)v, o, 64);
+    if (lane >= o && t > v) v = t;
+  }
+  return v;
+}
+
+// Block-wide max-scan of one value per thread: returns the maximum over the
+// threads before this one (INT64_MIN for thread 0), the block's in *total.
+__device__ inline int64_t block_excl_max(int64_t v, int64_t* lds4, int64_t* total) {
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t inc = wave_incl_max(v);
+  if (lane == 63) lds4[w] = inc;
+  int64_t pre = __shfl_up((long long)inc, 1, 64);
+  if (lane == 0) pre = INT64_MIN;
+  __syncthreads();
+  int64_t tot = INT64_MIN;
+#pragma unroll
+  for (int i = 0; i < kBlock / 64; i++) {
+    int64_t s = lds4[i];
+    if (i < w && s > pre) pre = s;
+    if (s > tot) tot = s;
+  }
+  __syncthreads();
+  *total = tot;
+  return pre;
+}
+
+__global__ __launch_bounds__(kBlock) void k_maxscan_reduce(const int64_t* in, int64_t n, int64_t* bmax) {
+  __shared__ int64_t lds[4];
+  int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
+  int64_t s = INT64_MIN;
+#pragma unroll
+  for (int i = 0; i < kScanItems; i++)
+    if (base + i < n && in[base + i] > s) s = in[base + i];
+  int64_t tot;
+  block_excl_max(s, lds, &tot);
+  if (threadIdx.x == 0) bmax[blockIdx.x] = tot;
+}
+
+// bpre[b]: the maximum of tiles 0 .. b (null: one tile)
+__global__ __launch_bounds__(kBlock) void k_maxscan_down(const int64_t* in, int64_t n, const int64_t* bpre,
+                                                         int64_t* out) {
+  __shared__ int64_t lds[4];
+  int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * kScanItems;
+  int64_t v[kScanItems];
+  int64_t s = INT64_MIN;
+#pragma unroll
+  for (int i = 0; i < kScanItems; i++) {
+    v[i] = (base + i < n) ? in[base + i] : INT64_MIN;
+    if (v[i] > s) s = v[i];
+  }
+  int64_t tot;
+  int64_t run = block_excl_max(s, lds, &tot);
+  if (bpre && blockIdx.x > 0) {
+    int64_t b = bpre[blockIdx.x - 1];
+    if (b > run) run = b;
+  }
+#pragma unroll
+  for (int i = 0; i < kScanItems; i++) {
+    if (v[i] > run) run = v[i];
+    if (base + i < n) out[base + i] = run;
+  }
+}
+
+static void maxscan_rec(const int64_t* in, int64_t* out, int64_t n, int64_t* scratch, hipStream_t s) {
+  int64_t nb = ceil_div(n, kScanTile);
+  if (nb <= 1) {
+    hipLaunchKernelGGL(k_maxscan_down, dim3(1), dim3(kBlock), 0, s, in, n, (const int64_t*)nullptr, out);
+    SHD_CHECK_LAUNCH();
+    return;
+  }
+  int64_t* bmax = scratch;
+  int64_t* bpre = scratch + nb;
+  hipLaunchKernelGGL(k_maxscan_reduce, dim3((unsigned)nb), dim3(kBlock), 0, s, in, n, bmax);
+  SHD_CHECK_LAUNCH();
+  maxscan_rec(bmax, bpre, nb, scratch + 2 * nb, s);
+  hipLaunchKernelGGL(k_maxscan_down, dim3((unsigned)nb), dim3(kBlock), 0, s, in, n, (const int64_t*)bpre, out);
+  SHD_CHECK_LAUNCH();
+}
+
+void scan_inclusive_max_i64(const int64_t* in, int64_t* out, int64_t n, DevBuf& scratch, hipStream_t s) {
+  if (n <= 0) return;
+  scratch.reserve(scan_need(n) * sizeof(int64_t));
+  maxscan_rec(in, out, n, scratch.as<int64_t>(), s);
+}
+
 // ============================================================ radix sort
 // (tile constants, digit helpers and the in-tile scatter: radix_tile.h)
 

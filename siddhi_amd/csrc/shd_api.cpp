@@ -147,6 +147,13 @@ Plan decode_plan(const int32_t* w, int64_t n) {
       if (nf < 0 || nf > 64) throw Error(SHD_E_INVALID_PLAN, "bad filter count");
       for (int i = 0; i < nf; i++) j.filters.push_back(r.next());
       if (j.stream < 0 || j.stream >= ns) throw Error(SHD_E_INVALID_PLAN, "bad join stream index");
+      if (j.wkind == SHD_W_EXTERNAL_TIME) {   // p packs the time attribute above the window time
+        j.ts_col = SHD_JOIN_EXT_TS_COL(j.param);
+        j.param = SHD_JOIN_EXT_TIME(j.param);
+        const auto& types = p.stream_types[j.stream];
+        if (j.ts_col >= (int)types.size() || types[j.ts_col] != SHD_T_LONG)
+          throw Error(SHD_E_INVALID_PLAN, "externalTime join side: the time attribute is not a LONG attribute");
+      }
     }
     p.join_on = r.next();
     if (p.join_on < -1 || p.join_on >= ne) throw Error(SHD_E_INVALID_PLAN, "bad join condition");

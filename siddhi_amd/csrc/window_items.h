@@ -44,6 +44,7 @@ struct XwArgs {
   int ncols;
   int nw;                           // state key words (partition key + group words), 0 = one state
   int64_t C, cap, seq0;
+  int notnull1;                     // 1 + the attribute an item needs non-null (a join side's event time), 0 = none
 };
 
 // flags[i]: bit0 passes the filters, bit1 has a (non-null) partition key
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_filter(const XwArgs* __restrict__
     }
     if (keyed) {
       f |= 2;
-      if (eval_filters(a.es, a.filters, cx)) f |= 1;
+      if (eval_filters(a.es, a.filters, cx) && !(a.notnull1 && col_load(a.cs, i, a.notnull1 - 1).null)) f |= 1;
     }
     flags[i] = f;
     pkey[i] = k;

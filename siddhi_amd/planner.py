@@ -833,10 +833,26 @@ def _plan_single(app, q, dictionary, partition, extra_streams) -> QueryPlan:
                      partition is not None, {si.stream: "single"})
 
 
+# an externalTime join side's parameter word (include/siddhi_ir.h, JOIN): the
+# window time in the low 48 bits, the time attribute's index above them
+JOIN_EXT_TIME_BITS = 48
+
+
+def join_ext_pack(ts_col: int, t: int) -> int:
+    return (ts_col << JOIN_EXT_TIME_BITS) | t
+
+
+def join_ext_unpack(p: int):
+    """(time attribute index, window time) of an externalTime join side."""
+    p &= (1 << 64) - 1
+    return p >> JOIN_EXT_TIME_BITS, p & ((1 << JOIN_EXT_TIME_BITS) - 1)
+
+
 def _plan_join(app, q, dictionary, partition, extra_streams) -> QueryPlan:
     """A stream-stream window join (JoinInputStreamParser.parseInputStream,
     C/util/parser/JoinInputStreamParser.java:88-352): each side is a defined
-    stream with filters and `length`, `time` or no window.  trigger: the side's
+    stream with filters and `length`, `externalTime`, `time` or no window
+    (`time` is refused once the query has passed validation).  trigger: the side's
     events look the other side up (both, or only the `unidirectional` one,
     :200-225); outer: a trigger of that side without a match still emits a row
     (:334-352: the left side of `left outer`, the right of `right outer`, both
@@ -893,9 +909,19 @@ def _plan_join(app, q, dictionary, partition, extra_streams) -> QueryPlan:
                 # refused below, once the query has passed the reference's own validation
                 refused = "time windows on a join side are outside the hot path"
                 continue
+            if h.name == "externaltime":
+                _, wkind, t, col = _window_handler(h, False, metas[i], s.stream)
+                if t <= 0:
+                    raise UnsupportedPlanException("externalTime with a window time of 0 or less on a join side "
+                                                   "is outside the hot path")
+                if t >= 1 << JOIN_EXT_TIME_BITS:
+                    raise UnsupportedPlanException("externalTime with a window time of 2^48 or more on a join side "
+                                                   "is outside the hot path")
+                param = join_ext_pack(col, t)
+                continue
             if h.name != "length":
-                raise UnsupportedPlanException("window %s on a join side is outside the hot path (length or none)"
-                                               % h.name)
+                raise UnsupportedPlanException("window %s on a join side is outside the hot path "
+                                               "(length, externalTime or none)" % h.name)
             _, wkind, param, _ = _window_handler(h, False)
             if param <= 0:
                 raise UnsupportedPlanException("length(0) on a join side is outside the hot path")
