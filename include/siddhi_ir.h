@@ -147,7 +147,18 @@ enum shd_etb_start { SHD_ETB_START_NONE = 0, SHD_ETB_START_CONST = 1, SHD_ETB_ST
 /* The p word of an externalTime side of a JOIN plan. */
 #define SHD_JOIN_EXT_TIME(p) ((long long)((unsigned long long)(p) & 0xFFFFFFFFFFFFull))
 #define SHD_JOIN_EXT_TS_COL(p) ((int)(((unsigned long long)(p) >> 48) & 0xFFFF))
-enum shd_agg { SHD_AGG_SUM = 1, SHD_AGG_AVG = 2, SHD_AGG_COUNT = 3 };
+/* Aggregators (C/query/selector/attribute/aggregator/).  SUM / AVG / COUNT keep
+ * three scalars per state.  MAX / MIN ({Max,Min}AttributeAggregatorExecutor.java)
+ * return the argument's type (INT, LONG, FLOAT or DOUBLE, no widening) and keep
+ * a value plus, in tracking mode, a deque of values; the plan does not store
+ * the mode, every consumer derives it as the reference does (:93-96): tracking
+ * iff the window is a sliding one (LENGTH, TIME, TIME_LENGTH, EXTERNAL_TIME:
+ * ProcessingMode.SLIDE) or expired_on is set.  MAX_FOREVER / MIN_FOREVER
+ * ({Max,Min}ForeverAttributeAggregatorExecutor.java) fold adds and removes
+ * alike into one value and keep it over a RESET.  A plan with any of the four
+ * runs on the keyed window engine only. */
+enum shd_agg { SHD_AGG_SUM = 1, SHD_AGG_AVG = 2, SHD_AGG_COUNT = 3, SHD_AGG_MAX = 4, SHD_AGG_MIN = 5,
+               SHD_AGG_MAX_FOREVER = 6, SHD_AGG_MIN_FOREVER = 7 };
 
 /* Output / input event types (ComplexEvent.Type). */
 enum shd_evtype { SHD_EV_CURRENT = 0, SHD_EV_EXPIRED = 1, SHD_EV_TIMER = 2, SHD_EV_RESET = 3 };

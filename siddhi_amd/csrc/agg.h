@@ -3,7 +3,9 @@
 // Sum / Avg / Count AttributeAggregatorExecutor (C/query/selector/attribute/
 // aggregator/*.java: processAdd / processRemove): one CURRENT (add) or EXPIRED
 // (remove) operand at a time, in the reference's order, so every double sum is
-// the same IEEE result (built with -ffp-contract=off).
+// the same IEEE result (built with -ffp-contract=off).  Below them the
+// {Max,Min}[Forever]AttributeAggregatorExecutor steps (mm_step): a value and,
+// in tracking mode, the reference's deque, restated with its quirk.
 #pragma once
 #include "engine.h"
 
@@ -86,6 +88,130 @@ __device__ __forceinline__ void agg_step(int kind, int type, bool add, uint64_t 
       break;
     }
   }
+}
+
+// ---------------------------------------------------------------- min / max
+// {Max,Min}AttributeAggregatorExecutor.java:84-150 with their state classes
+// (:152-), {Max,Min}ForeverAttributeAggregatorExecutor.java:119-200.  A state is
+// a value with its null flag and, in tracking mode (processing mode SLIDE or
+// expired output, :93-96), a deque of values.  The executors are restated as
+// they are, not as a sliding extremum: an add pops the back while it compares
+// below (max) / above (min) the new value, a remove is removeFirstOccurrence
+// by equals() and leaves peekFirst() as the value -- removing a value an
+// earlier add already popped takes a later event's equal value with it.
+__device__ __forceinline__ bool agg_is_minmax(int kind) { return kind >= SHD_AGG_MAX; }
+
+// a < b on the unboxed values (Java's <: false against NaN); INT is the signed
+// low word of the slot, FLOAT compares as float
+__device__ __forceinline__ bool mm_lt(int type, uint64_t a, uint64_t b) {
+  switch (type) {
+    case SHD_T_INT: return v_i32(a) < v_i32(b);
+    case SHD_T_LONG: return (int64_t)a < (int64_t)b;
+    case SHD_T_FLOAT: return v_f32(a) < v_f32(b);
+    default: return v_f64(a) < v_f64(b);
+  }
+}
+// a gives way to b: a < b for max, a > b for min
+__device__ __forceinline__ bool mm_below(bool is_max, int type, uint64_t a, uint64_t b) {
+  return is_max ? mm_lt(type, a, b) : mm_lt(type, b, a);
+}
+__device__ __forceinline__ bool mm_isnan(int type, uint64_t a) {
+  if (type == SHD_T_FLOAT) return v_f32(a) != v_f32(a);
+  if (type == SHD_T_DOUBLE) return v_f64(a) != v_f64(a);
+  return false;
+}
+// equals() of the boxed values compares these: Integer / Long by value, Float /
+// Double by floatToIntBits / doubleToLongBits (every NaN equal, 0.0 != -0.0)
+__device__ __forceinline__ uint64_t mm_bits(int type, uint64_t a) {
+  switch (type) {
+    case SHD_T_INT: return (uint64_t)(uint32_t)a;
+    case SHD_T_LONG: return a;
+    case SHD_T_FLOAT: return mm_isnan(type, a) ? 0x7fc00000ull : (uint64_t)(uint32_t)a;
+    default: return mm_isnan(type, a) ? 0x7ff8000000000000ull : a;
+  }
+}
+
+// One state's deque while a push folds it: the live elements are w[h, t) of
+// the lane's own region of `room` slots (the carried deque copied to its
+// front; every add appends at most one element).
+struct MmDeque {
+  uint64_t* w;
+  int64_t h, t, room;
+};
+
+// The deque position of removeFirstOccurrence(x), -1 when absent.  While no
+// NaN has entered the deque since it was last empty it is monotone (max:
+// non-increasing), so the elements numerically equal to x are one run found by
+// two binary searches, and equals() is decided inside that run alone (it
+// separates 0.0 from -0.0).  After a NaN the order is lost: the literal scan.
+__device__ __forceinline__ int64_t mm_find(bool is_max, int type, const MmDeque& q, bool had_nan, uint64_t x) {
+  const uint64_t xb = mm_bits(type, x);
+  int64_t lo = q.h, hi = q.t;
+  if (!had_nan) {
+    if (mm_isnan(type, x)) return -1;
+    int64_t e = q.t;
+    while (lo < e) {   // first element that does not beat x
+      const int64_t mid = (lo + e) >> 1;
+      if (mm_below(is_max, type, x, q.w[mid])) lo = mid + 1;
+      else e = mid;
+    }
+    hi = lo;
+    e = q.t;
+    while (hi < e) {   // first element x beats
+      const int64_t mid = (hi + e) >> 1;
+      if (!mm_below(is_max, type, q.w[mid], x)) hi = mid + 1;
+      else e = mid;
+    }
+  }
+  for (int64_t i = lo; i < hi; i++)
+    if (mm_bits(type, q.w[i]) == xb) return i;
+  return -1;
+}
+
+// One step of a min / max / minForever / maxForever state.  val: the value's
+// payload; flags: bit 0 the value is set (non-null), bit 1 the deque has taken
+// a NaN since it was last empty; q: the tracking deque, null without tracking.
+// ob / on: the aggregator's value after the step, in the argument's type.
+__device__ __forceinline__ void mm_step(int kind, int type, bool add, uint64_t x, bool xn, uint64_t& val,
+                                        int64_t& flags, MmDeque* q, uint64_t& ob, bool& on) {
+  const bool is_max = kind == SHD_AGG_MAX || kind == SHD_AGG_MAX_FOREVER;
+  bool has = (flags & 1) != 0;
+  if (xn) {
+    // a null argument leaves the state alone (processAdd / processRemove :120-139)
+  } else if (kind == SHD_AGG_MAX_FOREVER || kind == SHD_AGG_MIN_FOREVER) {
+    // add and remove alike (MaxForever...StateDouble :158-174)
+    if (!has || mm_below(is_max, type, val, x)) val = x;
+    has = true;
+  } else if (add) {
+    if (q) {
+      while (q->t > q->h && mm_below(is_max, type, q->w[q->t - 1], x)) q->t--;   // descendingIterator (:167-173)
+      if (q->t == q->h) flags &= ~(int64_t)2;
+      if (q->t < q->room) q->w[q->t++] = x;                                      // addLast (:174)
+      if (mm_isnan(type, x)) flags |= 2;
+    }
+    if (!has || mm_below(is_max, type, val, x)) val = x;   // :176-178
+    has = true;
+  } else if (q) {
+    const int64_t i = mm_find(is_max, type, *q, (flags & 2) != 0, x);   // removeFirstOccurrence (:185)
+    if (i >= 0) {
+      // close the gap from the shorter side
+      if (i - q->h <= q->t - 1 - i) {
+        for (int64_t j = i; j > q->h; j--) q->w[j] = q->w[j - 1];
+        q->h++;
+      } else {
+        for (int64_t j = i; j + 1 < q->t; j++) q->w[j] = q->w[j + 1];
+        q->t--;
+      }
+    }
+    has = q->t > q->h;   // peekFirst (:186)
+    if (has) val = q->w[q->h];
+    else flags &= ~(int64_t)2;
+  } else if (has && mm_bits(type, val) == mm_bits(type, x)) {
+    has = false;   // without tracking: maxValue.equals(data) (:188-190)
+  }
+  flags = (flags & ~(int64_t)1) | (has ? 1 : 0);
+  ob = has ? val : 0;
+  on = !has;
 }
 
 }  // namespace

@@ -3830,6 +3830,10 @@ std::unique_ptr<Engine> make_single_engine(const Plan& p, std::string& why) {
   if (e->nagg > kMaxAggs) { why = "too many aggregators"; return nullptr; }
   e->partitioned = !p.part_keys.empty();
   bool needs_agg = e->nagg > 0 || !p.group_by.empty();
+  // min / max / minForever / maxForever: their state is not three scalars; the
+  // keyed window engine alone folds them, whatever the window and output
+  for (auto& a : p.aggs)
+    if (a.kind > SHD_AGG_COUNT) return make_window_x_engine(p, why);
   // batch windows (flush chunks with RESET) and timeLength: the window-x engine
   if (e->wkind == SHD_W_LENGTH_BATCH || e->wkind == SHD_W_TIME_BATCH || e->wkind == SHD_W_TIME_LENGTH ||
       e->wkind == SHD_W_EXTERNAL_TIME || e->wkind == SHD_W_TIME_BATCH_STREAM ||

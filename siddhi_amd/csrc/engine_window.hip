@@ -11,6 +11,8 @@
 //   query/selector/QuerySelector.java:76-99 (process), :161-205 (processNoGroupBy),
 //     :271-313 (processInBatchNoGroupBy), :315-373 (processInBatchGroupBy)
 //   query/selector/attribute/aggregator/{Sum,Avg,Count}AttributeAggregatorExecutor.java
+//   query/selector/attribute/aggregator/{Max,Min,MaxForever,MinForever}AttributeAggregatorExecutor.java
+//     (every plan with one of these runs here: k_xw_fold<true> and the deque store)
 //   partition/PartitionStreamReceiver.java:175-216 (same-key runs = chunks)
 //   util/snapshot/state/PartitionStateHolder.java:43-69 (state per (partition key,
 //     group key); a window state is dropped when its queue empties)
@@ -461,7 +463,23 @@ struct FoldArgsX {
   uint8_t* resn;
   uint8_t* rowflag;   // [nops]
   uint32_t* rowsrc;
+  // min / max states keep their value in lsum and their flags in cnt (agg.h
+  // mm_step).  Tracking deques: dq[g] = the deque row of aggregator g (-1:
+  // none).  Carried deques: row d, state s holds dq_len[d * nstates + s]
+  // values at dq_val + dq_off[...]; during the fold each lane owns the region
+  // dq_work + dq_woff[lane * ndq + d] and leaves the length and the place of
+  // what is left in dq_nlen / dq_nsrc (kDqWork: in the work area).
+  int ndq;
+  int dq[kMaxAggs];
+  const uint32_t* dq_len;
+  const uint32_t* dq_off;
+  const uint64_t* dq_val;
+  const uint32_t* dq_woff;
+  uint64_t* dq_work;
+  uint32_t* dq_nlen;
+  uint32_t* dq_nsrc;
 };
+constexpr uint32_t kDqWork = 0x80000000u;
 
 // Aggregated value of one aggregator after a step (avg divided here).
 __device__ __forceinline__ void agg_value(int kind, uint64_t ob, bool on, int64_t c, uint64_t& v, uint8_t& vn) {
@@ -474,6 +492,9 @@ __device__ __forceinline__ void agg_value(int kind, uint64_t ob, bool on, int64_
 // state's operations in the reference's order.  The selector's pick per chunk
 // is tracked on the fly: a run = the state's consecutive operations of one
 // chunk; its first and last selected ("on") operations decide the row.
+// MM: the plan has min / max aggregators (the plain instance is the kernel
+// the sum / avg / count plans have always run).
+template <bool MM>
 __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict__ ap, const uint32_t* heads,
                                                     int64_t nheads, const uint32_t* ssid, const uint32_t* sq) {
   const FoldArgsX& a = *ap;
@@ -488,6 +509,20 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
       l[g] = a.lsum[(int64_t)g * a.nstates + sid];
       c[g] = a.cnt[(int64_t)g * a.nstates + sid];
     }
+    MmDeque dq[MM ? kMaxAggs : 1];
+    if constexpr (MM) {
+      // the carried deques move to the front of the lane's regions
+      for (int k = 0; k < a.ndq; k++) {
+        const int64_t cell = (int64_t)k * a.nstates + sid;
+        const int64_t n0 = a.dq_len[cell];
+        const uint64_t* src = a.dq_val + a.dq_off[cell];
+        dq[k].w = a.dq_work + a.dq_woff[hh * a.ndq + k];
+        dq[k].h = 0;
+        dq[k].t = n0;
+        dq[k].room = n0 + (q1 - q0);
+        for (int64_t i = 0; i < n0; i++) dq[k].w[i] = src[i];
+      }
+    }
     int64_t ep = a.epoch ? a.epoch[sid] : 0;
     uint32_t cur = 0xFFFFFFFFu;
     int64_t first = -1, last = -1;
@@ -499,6 +534,11 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
         // a RESET came after this state's last operation
         ep = a.op_epoch[q];
         for (int g = 0; g < a.nagg; g++) {
+          if constexpr (MM) {
+            // reset(): min / max clear value and deque, the Forever kinds keep theirs
+            if (a.kind[g] == SHD_AGG_MAX_FOREVER || a.kind[g] == SHD_AGG_MIN_FOREVER) continue;
+            if (a.dq[g] >= 0) dq[a.dq[g]].h = dq[a.dq[g]].t;
+          }
           d[g] = 0.0;
           l[g] = 0;
           c[g] = 0;
@@ -509,8 +549,15 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
       for (int g = 0; g < a.nagg; g++) {
         uint64_t ob;
         bool on;
-        agg_step(a.kind[g], a.type[g], add, a.argv[(int64_t)g * a.cap + it], a.argn[(int64_t)g * a.cap + it] != 0,
-                 d[g], l[g], c[g], ob, on);
+        const uint64_t xb = a.argv[(int64_t)g * a.cap + it];
+        const bool xn = a.argn[(int64_t)g * a.cap + it] != 0;
+        if (MM && agg_is_minmax(a.kind[g])) {
+          uint64_t v = (uint64_t)l[g];
+          mm_step(a.kind[g], a.type[g], add, xb, xn, v, c[g], a.dq[g] >= 0 ? &dq[a.dq[g]] : nullptr, ob, on);
+          l[g] = (int64_t)v;
+        } else {
+          agg_step(a.kind[g], a.type[g], add, xb, xn, d[g], l[g], c[g], ob, on);
+        }
         agg_value(a.kind[g], ob, on, c[g], vv[g], vn[g]);
       }
       bool sel = a.op_on[q] != 0;
@@ -546,6 +593,41 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
       a.cnt[(int64_t)g * a.nstates + sid] = c[g];
     }
     if (a.epoch) a.epoch[sid] = ep;
+    if constexpr (MM) {
+      for (int k = 0; k < a.ndq; k++) {
+        const int64_t cell = (int64_t)k * a.nstates + sid;
+        a.dq_nlen[cell] = (uint32_t)(dq[k].t - dq[k].h);
+        a.dq_nsrc[cell] = (a.dq_woff[hh * a.ndq + k] + (uint32_t)dq[k].h) | kDqWork;
+      }
+    }
+  }
+}
+
+// Room of each lane's deque regions: the carried deque plus one slot per
+// operation of the state in this push (an add appends at most one value).
+__global__ __launch_bounds__(kBlock) void k_xw_dq_room(const uint32_t* heads, int64_t nheads, int64_t nops,
+                                                       const uint32_t* ssid, int ndq, int64_t nstates,
+                                                       const uint32_t* dq_len, uint32_t* room) {
+  for (int64_t hh = (int64_t)blockIdx.x * kBlock + threadIdx.x; hh < nheads; hh = nheads) {
+    const int64_t q0 = heads[hh];
+    const int64_t q1 = hh + 1 < nheads ? (int64_t)heads[hh + 1] : nops;
+    const uint32_t sid = ssid[q0];
+    for (int k = 0; k < ndq; k++) room[hh * ndq + k] = dq_len[(int64_t)k * nstates + sid] + (uint32_t)(q1 - q0);
+  }
+}
+
+// The deques after the fold, packed into the other slot of the store: value e
+// of the new store belongs to the last cell whose offset is <= e (empty cells
+// share their successor's offset); its source is the work area for the states
+// this push folded, the old store for the rest.
+__global__ __launch_bounds__(kBlock) void k_xw_dq_pack(int64_t total, int64_t ncell, const uint32_t* noff,
+                                                       const uint32_t* nsrc, const uint64_t* old_val,
+                                                       const uint64_t* work, uint64_t* dst) {
+  for (int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x; e < total; e = total) {
+    const int64_t cell = upper_bound(noff, (int64_t)0, ncell, (uint32_t)e) - 1;
+    const uint32_t src = nsrc[cell];
+    const int64_t i = e - noff[cell];
+    dst[e] = (src & kDqWork) ? work[(src & ~kDqWork) + i] : old_val[src + i];
   }
 }
 
@@ -1300,6 +1382,17 @@ struct WindowXEngine : Engine {
   // aggregator states [nagg][nstates]
   DevBuf g_dsum, g_lsum, g_cnt;
   int64_t nstates = 0;
+  // min / max: `mm` the plan has such aggregators (k_xw_fold<true>), `track`
+  // their tracking mode.  The deque store of the ndq tracking ones: lengths and
+  // offsets [ndq][nstates], the values packed in slot dq_cur of dq_val
+  // (double-buffered like the items: a push reads one slot and packs what is
+  // left into the other, which grows by doubling).
+  bool mm = false, track = false;
+  int ndq = 0;
+  int dq_of[kMaxAggs] = {};
+  DevBuf dq_len, dq_off, dq_val[2];
+  int dq_cur = 0;
+  int64_t dq_total = 0;
   // batch windows: per state its RESET epoch (k_xw_fold); timeBatch's
   // processor-level nextEmitTime and the Scheduler's notify queue (FIFO)
   bool batch = false;
@@ -1336,6 +1429,8 @@ struct WindowXEngine : Engine {
   DevBuf eopp, nops_b, opscan, op_item, op_add, op_on, op_chunk, op_now, op_seq;
   // fold and row selection
   DevBuf osid, osid2, oq, oq2, ohead, ohoff, ohl, resv, resn, rowflag, rowsrc, roff;
+  // min / max deques: the lanes' regions, what the fold leaves
+  DevBuf dq_room, dq_woff, dq_work, dq_nlen, dq_noff, dq_nsrc;
   // emit
   DevBuf rkey, rkey2, rq, rq2;
   // carry and pending
@@ -1378,7 +1473,10 @@ struct WindowXEngine : Engine {
       SHD_HIP(hipMemsetAsync(g_lsum.p, 0, g_lsum.cap, stream));
       SHD_HIP(hipMemsetAsync(g_cnt.p, 0, g_cnt.cap, stream));
       if (g_epoch.p) SHD_HIP(hipMemsetAsync(g_epoch.p, 0xFF, g_epoch.cap, stream));
+      if (dq_len.p) SHD_HIP(hipMemsetAsync(dq_len.p, 0, dq_len.cap, stream));
+      if (dq_off.p) SHD_HIP(hipMemsetAsync(dq_off.p, 0, dq_off.cap, stream));
     }
+    dq_total = 0;
   }
 
   // ---- storage
@@ -1394,14 +1492,15 @@ struct WindowXEngine : Engine {
       });
     items.cur = to;
   }
-  // A [rows][n] table of 8-byte cells becomes [rows][n2]: new cells are filled
-  // with `fill` bytes, the old rows copied.
-  void grow_table(DevBuf& t, int rows, int64_t n, int64_t n2, int fill) {
+  // A [rows][n] table of 8-byte cells (`cell` bytes) becomes [rows][n2]: new
+  // cells are filled with `fill` bytes, the old rows copied.
+  void grow_table(DevBuf& t, int rows, int64_t n, int64_t n2, int fill, size_t cell = 8) {
     DevBuf g;
-    g.reserve((size_t)rows * n2 * 8);
-    SHD_HIP(hipMemsetAsync(g.p, fill, (size_t)rows * n2 * 8, stream));
+    g.reserve((size_t)rows * n2 * cell);
+    SHD_HIP(hipMemsetAsync(g.p, fill, (size_t)rows * n2 * cell, stream));
     for (int r = 0; r < rows && n; r++)
-      SHD_HIP(hipMemcpyAsync(g.as<int64_t>() + r * n2, t.as<int64_t>() + r * n, n * 8, hipMemcpyDeviceToDevice, stream));
+      SHD_HIP(hipMemcpyAsync(g.as<char>() + (size_t)r * n2 * cell, t.as<char>() + (size_t)r * n * cell, n * cell,
+                             hipMemcpyDeviceToDevice, stream));
     SHD_HIP(hipStreamSynchronize(stream));
     t.swap(g);
   }
@@ -1411,6 +1510,10 @@ struct WindowXEngine : Engine {
     grow_table(g_lsum, nagg, nstates, ns, 0);
     grow_table(g_cnt, nagg, nstates, ns, 0);
     if (batch) grow_table(g_epoch, 1, nstates, ns, 0xFF);
+    if (ndq > 0) {
+      grow_table(dq_len, ndq, nstates, ns, 0, 4);
+      grow_table(dq_off, ndq, nstates, ns, 0, 4);
+    }
     nstates = ns;
   }
   void ensure_states(int64_t n) {
@@ -2194,9 +2297,8 @@ struct WindowXEngine : Engine {
     fa.resn = resn.as<uint8_t>();
     fa.rowflag = rowflag.as<uint8_t>();
     fa.rowsrc = rowsrc.as<uint32_t>();
-    const FoldArgsX* d_fa = dev_args(fa);
     if (plain) {
-      launch(k_xw_plain_rows, nops, d_fa);
+      launch(k_xw_plain_rows, nops, dev_args(fa));
     } else {
       // one lane per state: the operations grouped by state id, in order
       SHD_HIP(hipMemsetAsync(rowflag.p, 0, nops, stream));
@@ -2215,11 +2317,65 @@ struct WindowXEngine : Engine {
       const int64_t nheads = scan(ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops);
       ohl.reserve(std::max<int64_t>(nheads, 1) * 4);
       launch(k_head_list, nops, ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops, ohl.as<uint32_t>());
-      launch(k_xw_fold, nheads, d_fa, ohl.as<uint32_t>(), nheads, ssid, sq);
+      if (!mm) {
+        launch(k_xw_fold<false>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
+      } else {
+        fold_minmax(fa, nheads, ssid, sq);
+      }
     }
     mark("fold");
     roff.reserve(nops * 4);
     P.nrows = scan_u8_flags(rowflag.as<uint8_t>(), nops);
+  }
+
+  // The fold of a plan with min / max aggregators.  Tracking deques: every
+  // lane (a state with operations in this push) gets one region per deque,
+  // sized by its carried length plus its operations and placed by one
+  // exclusive scan, so no lane allocates or waits; after the fold the deques of
+  // all states -- folded ones from the work area, the rest from the old slot --
+  // are packed into the other slot of the store (lengths, scan, copy).
+  void fold_minmax(FoldArgsX& fa, int64_t nheads, const uint32_t* ssid, const uint32_t* sq) {
+    const int64_t nops = fa.nops;
+    const int64_t ncell = (int64_t)ndq * nstates;
+    fa.ndq = ndq;
+    for (int g = 0; g < nagg; g++) fa.dq[g] = dq_of[g];
+    if (ndq > 0) {
+      if ((int64_t)ndq * nops + dq_total >= (int64_t)INT32_MAX)
+        throw Error(SHD_E_CAPACITY, "min / max deques exceed 2^31 values");
+      const int64_t nr = nheads * ndq;
+      dq_room.reserve(nr * 4);
+      dq_woff.reserve(nr * 4);
+      launch(k_xw_dq_room, nheads, ohl.as<uint32_t>(), nheads, nops, ssid, ndq, nstates, dq_len.as<uint32_t>(),
+             dq_room.as<uint32_t>());
+      const int64_t wtotal = scan(dq_room.as<uint32_t>(), dq_woff.as<uint32_t>(), nr);
+      dq_work.reserve(std::max<int64_t>(wtotal, 1) * 8);
+      dq_val[dq_cur].reserve(8);
+      dq_nlen.reserve(ncell * 4);
+      dq_noff.reserve(ncell * 4);
+      dq_nsrc.reserve(ncell * 4);
+      SHD_HIP(hipMemcpyAsync(dq_nlen.p, dq_len.p, ncell * 4, hipMemcpyDeviceToDevice, stream));
+      SHD_HIP(hipMemcpyAsync(dq_nsrc.p, dq_off.p, ncell * 4, hipMemcpyDeviceToDevice, stream));
+      fa.dq_len = dq_len.as<uint32_t>();
+      fa.dq_off = dq_off.as<uint32_t>();
+      fa.dq_val = dq_val[dq_cur].as<uint64_t>();
+      fa.dq_woff = dq_woff.as<uint32_t>();
+      fa.dq_work = dq_work.as<uint64_t>();
+      fa.dq_nlen = dq_nlen.as<uint32_t>();
+      fa.dq_nsrc = dq_nsrc.as<uint32_t>();
+    }
+    launch(k_xw_fold<true>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
+    if (ndq == 0) return;
+    const int64_t ntotal = scan(dq_nlen.as<uint32_t>(), dq_noff.as<uint32_t>(), ncell);
+    const int oth = dq_cur ^ 1;
+    if ((int64_t)(dq_val[oth].cap / 8) < ntotal)
+      dq_val[oth].reserve((size_t)std::max<int64_t>(ntotal, std::max<int64_t>(1024, (int64_t)(dq_val[oth].cap / 8) * 2)) * 8);
+    if (ntotal > 0)
+      launch(k_xw_dq_pack, ntotal, ntotal, ncell, dq_noff.as<uint32_t>(), dq_nsrc.as<uint32_t>(),
+             dq_val[dq_cur].as<uint64_t>(), dq_work.as<uint64_t>(), dq_val[oth].as<uint64_t>());
+    dq_len.swap(dq_nlen);
+    dq_off.swap(dq_noff);
+    dq_cur = oth;
+    dq_total = ntotal;
   }
 
   // rows in (chunk, position) order
@@ -2395,6 +2551,16 @@ struct WindowXEngine : Engine {
     w.put<int64_t>((int64_t)tb_notify.size());
     for (int64_t t : tb_notify) w.put<int64_t>(t);
     if (batch && nagg > 0 && nstates > 0) w.dev(g_epoch.p, (size_t)nstates * 8);
+    // min / max deques (the values and flags travel in the state tables above)
+    if (ndq > 0) {
+      w.put<int32_t>(ndq);
+      w.put<int64_t>(dq_total);
+      if (nstates > 0) {
+        w.dev(dq_len.p, (size_t)ndq * nstates * 4);
+        w.dev(dq_off.p, (size_t)ndq * nstates * 4);
+      }
+      if (dq_total > 0) w.dev(dq_val[dq_cur].p, (size_t)dq_total * 8);
+    }
   }
   void load_state(SnapR& r) override {
     const int64_t c0 = r.get<int64_t>();
@@ -2436,6 +2602,19 @@ struct WindowXEngine : Engine {
     const int64_t nn = r.get<int64_t>();
     for (int64_t i = 0; i < nn; i++) tb_notify.push_back(r.get<int64_t>());
     if (batch && nagg > 0 && nstates > 0) r.dev_into(g_epoch.p, (size_t)nstates * 8);
+    if (ndq > 0) {
+      if (r.get<int32_t>() != ndq) throw Error(SHD_E_ARG, "snapshot of a different plan");
+      dq_total = r.get<int64_t>();
+      if (dq_total < 0 || dq_total >= (int64_t)INT32_MAX) throw Error(SHD_E_ARG, "snapshot of a different plan");
+      if (nstates > 0) {
+        r.dev_into(dq_len.p, (size_t)ndq * nstates * 4);
+        r.dev_into(dq_off.p, (size_t)ndq * nstates * 4);
+      }
+      if (dq_total > 0) {
+        dq_val[dq_cur].reserve((size_t)dq_total * 8);
+        r.dev_into(dq_val[dq_cur].p, (size_t)dq_total * 8);
+      }
+    }
     counters.carry = C;
   }
 };
@@ -2501,6 +2680,20 @@ std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why) {
   if (p.outputs.size() > (size_t)kMaxCols) { why = "too many outputs"; return nullptr; }
   e->nagg = (int)p.aggs.size();
   if (e->nagg > kMaxAggs) { why = "too many aggregators"; return nullptr; }
+  // min / max track future states when the window slides or the query emits
+  // EXPIRED events (MaxAttributeAggregatorExecutor.java:93-96; SLIDE is
+  // SlidingWindowProcessor.java:90, every other window here is BATCH or RESET)
+  e->track = e->wkind == SHD_W_LENGTH || e->wkind == SHD_W_TIME || e->wkind == SHD_W_TIME_LENGTH ||
+             e->wkind == SHD_W_EXTERNAL_TIME || p.expired_on;
+  for (int g = 0; g < e->nagg; g++) {
+    const auto& a = p.aggs[g];
+    e->dq_of[g] = -1;
+    if (a.kind < SHD_AGG_SUM || a.kind > SHD_AGG_MIN_FOREVER) { why = "unknown aggregator"; return nullptr; }
+    if (a.kind < SHD_AGG_MAX) continue;
+    if (a.expr < 0 || a.type < SHD_T_INT || a.type > SHD_T_DOUBLE) { why = "min / max of a non-numeric argument"; return nullptr; }
+    e->mm = true;
+    if (e->track && (a.kind == SHD_AGG_MAX || a.kind == SHD_AGG_MIN)) e->dq_of[g] = e->ndq++;
+  }
   e->partitioned = !p.part_keys.empty();
   if (e->partitioned) {
     e->key_expr = p.part_keys[0].second;

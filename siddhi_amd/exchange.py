@@ -458,6 +458,10 @@ def window_of(qp) -> Optional[Tuple[str, int]]:
     """("length", L) or ("time", T ms) of a single-stream window query (planner
     Plan.handlers), None without a window."""
     from . import planner as pl
+    if any(a[0] > pl.AGG_COUNT for a in qp.plan.aggs):
+        # their deques depend on values that left the window long ago (DESIGN.md §4.4.1), the
+        # Forever kinds on the whole stream: a halo does not rebuild that state
+        raise pl.UnsupportedPlanException("slices with a halo cannot rebuild min / max aggregator state")
     for h in qp.plan.handlers:
         if h[0] == pl.H_WINDOW:
             if h[1] not in (pl.W_LENGTH, pl.W_TIME):

@@ -14,7 +14,9 @@ Restates the reference planning rules the hot path depends on:
   relational ops use Java binary promotion; == / != on (Float, Long) or
   (Long, Float) compare as double,
 * aggregator return types (SumAttributeAggregatorExecutor.java:84-134: INT/LONG
-  -> LONG, FLOAT/DOUBLE -> DOUBLE; avg -> DOUBLE; count -> LONG).
+  -> LONG, FLOAT/DOUBLE -> DOUBLE; avg -> DOUBLE; count -> LONG; min / max /
+  minForever / maxForever -> the argument's type, MaxAttributeAggregatorExecutor
+  .java:97).
 """
 from __future__ import annotations
 
@@ -46,6 +48,9 @@ W_TIME_BATCH_STREAM = 7
 W_EXTERNAL_TIME_BATCH = 8
 INT64_MIN = -(1 << 63)
 AGG_SUM, AGG_AVG, AGG_COUNT = 1, 2, 3
+AGG_MAX, AGG_MIN, AGG_MAX_FOREVER, AGG_MIN_FOREVER = 4, 5, 6, 7
+# function name (lower case) -> kind: the aggregators that return their argument's type
+_MINMAX_KIND = {"max": AGG_MAX, "min": AGG_MIN, "maxforever": AGG_MAX_FOREVER, "minforever": AGG_MIN_FOREVER}
 UNKNOWN_STATE = -1
 NUMERIC_RANK = {T_INT: 0, T_LONG: 1, T_FLOAT: 2, T_DOUBLE: 3}
 ARITH_OPS = {"+": OP_ADD, "-": OP_SUB, "*": OP_MUL, "/": OP_DIV, "%": OP_MOD}
@@ -355,6 +360,23 @@ class ExprCompiler:
                     rt = (T_LONG if at in (T_INT, T_LONG) else T_DOUBLE) if name == "sum" else T_DOUBLE
                 code.append((OP_AGG, len(self.plan.aggs) - 1, 0, 0))
                 return rt
+            if e.namespace is None and name in _MINMAX_KIND:
+                # {Max,Min}[Forever]AttributeAggregatorExecutor.init (C/query/selector/attribute/
+                # aggregator/MaxAttributeAggregatorExecutor.java:84-113): exactly one parameter,
+                # INT / LONG / FLOAT / DOUBLE, returned in its own type; anything else fails
+                # the app's creation (OperationNotSupportedException -> SiddhiAppCreationException)
+                if not self.agg_allowed:
+                    raise SiddhiAppValidationException("aggregator %s not allowed here" % e.name)
+                if len(e.args) != 1:
+                    raise SiddhiAppCreationException("%s aggregator has to have exactly 1 parameter, currently %d "
+                                                     "parameters provided" % (e.name, len(e.args)))
+                sub = ExprCompiler(self.plan, self.dict, self.metas, self.state_query)
+                arg, at = sub.compile(e.args[0], cs, di)
+                if at not in NUMERIC_RANK:
+                    raise SiddhiAppCreationException("%s not supported for %s" % (e.name, TYPE_NAME.get(at)))
+                self.plan.aggs.append((_MINMAX_KIND[name], arg, at))
+                code.append((OP_AGG, len(self.plan.aggs) - 1, 0, 0))
+                return at
             if e.namespace is None and name == "eventtimestamp" and not e.args:
                 code.append((OP_TS, 0, IDX_CURRENT, 0))
                 return T_LONG
@@ -640,7 +662,7 @@ def _plan_selector(plan: Plan, q: qc.Query, ec: ExprCompiler, metas: List[Meta],
     return names, types
 
 
-_AGG_FUNCS = ("sum", "avg", "count")
+_AGG_FUNCS = ("sum", "avg", "count") + tuple(_MINMAX_KIND)
 _INSTANCE_OF = {"instanceofboolean": T_BOOL, "instanceofdouble": T_DOUBLE, "instanceoffloat": T_FLOAT,
                 "instanceofinteger": T_INT, "instanceoflong": T_LONG, "instanceofstring": T_STRING}
 
@@ -654,6 +676,19 @@ def _has_agg(e) -> bool:
         return _has_agg(e.left) or _has_agg(e.right)
     if isinstance(e, (qc.Not, qc.IsNull)):
         return _has_agg(e.expr)
+    return False
+
+
+def _has_minmax(e) -> bool:
+    """Whether an expression holds a min / max / minForever / maxForever aggregator."""
+    if isinstance(e, qc.Func):
+        if e.namespace is None and e.name.lower() in _MINMAX_KIND:
+            return True
+        return any(_has_minmax(a) for a in e.args)
+    if isinstance(e, qc.BinOp):
+        return _has_minmax(e.left) or _has_minmax(e.right)
+    if isinstance(e, (qc.Not, qc.IsNull)):
+        return _has_minmax(e.expr)
     return False
 
 
@@ -1145,6 +1180,8 @@ def share_signature(q: qc.Query) -> Optional[str]:
     if isinstance(q.input, qc.StateInput) and (sel.group_by or sel.having is not None or
                                                any(_has_agg(oa.expr) for oa in sel.attrs)):
         return None   # aggregating / having selectors over state output run per query (IR POST section)
+    if any(_has_minmax(oa.expr) for oa in sel.attrs) or (sel.having is not None and _has_minmax(sel.having)):
+        return None   # min / max run on the keyed window engine alone: no shared segmented-scan pass
     import copy
     if _e1_site(q) is not None:
         q2 = copy.deepcopy(q)
