@@ -163,9 +163,10 @@ int shd_set_time(shd_query* q, int64_t ts);
  *     reset, which can cancel to far below its operands -- is caught by the
  *     guard's sign channel and also takes the exact fold (int operands are
  *     exempt: their sums are exact; long operands by value), so the default
- *     needs no option for it.  Plans with min / max / minForever / maxForever
- *     (SHD_AGG_MAX .. SHD_AGG_MIN_FOREVER) always run the sequential fold of
- *     the keyed window engine: the option is a no-op for them. */
+ *     needs no option for it.  Plans with min / max / minForever / maxForever,
+ *     stdDev, distinctCount, and, or (SHD_AGG_MAX .. SHD_AGG_OR) always run the
+ *     sequential fold of the keyed window engine: the option is a no-op for
+ *     them. */
 int shd_set_option(shd_query* q, const char* key, int64_t value);
 int shd_push(shd_query* q, const shd_batch* batch);
 int shd_flush(shd_query* q);                  /* wait for queued device work      */

@@ -155,10 +155,16 @@ enum shd_etb_start { SHD_ETB_START_NONE = 0, SHD_ETB_START_CONST = 1, SHD_ETB_ST
  * iff the window is a sliding one (LENGTH, TIME, TIME_LENGTH, EXTERNAL_TIME:
  * ProcessingMode.SLIDE) or expired_on is set.  MAX_FOREVER / MIN_FOREVER
  * ({Max,Min}ForeverAttributeAggregatorExecutor.java) fold adds and removes
- * alike into one value and keep it over a RESET.  A plan with any of the four
- * runs on the keyed window engine only. */
+ * alike into one value and keep it over a RESET.  STDDEV (StdDevAttribute
+ * AggregatorExecutor.java: INT / LONG / FLOAT / DOUBLE argument) returns DOUBLE,
+ * DISTINCT_COUNT (DistinctCount...: INT / LONG / FLOAT / DOUBLE / STRING / BOOL
+ * argument; null is a key) returns LONG and keeps a list of (key, count) pairs
+ * per state, AND / OR ({And,Or}...: BOOL argument) return BOOL and are never
+ * null.  A plan with any kind above COUNT runs on the keyed window engine
+ * only. */
 enum shd_agg { SHD_AGG_SUM = 1, SHD_AGG_AVG = 2, SHD_AGG_COUNT = 3, SHD_AGG_MAX = 4, SHD_AGG_MIN = 5,
-               SHD_AGG_MAX_FOREVER = 6, SHD_AGG_MIN_FOREVER = 7 };
+               SHD_AGG_MAX_FOREVER = 6, SHD_AGG_MIN_FOREVER = 7, SHD_AGG_STDDEV = 8, SHD_AGG_DISTINCT_COUNT = 9,
+               SHD_AGG_AND = 10, SHD_AGG_OR = 11 };
 
 /* Output / input event types (ComplexEvent.Type). */
 enum shd_evtype { SHD_EV_CURRENT = 0, SHD_EV_EXPIRED = 1, SHD_EV_TIMER = 2, SHD_EV_RESET = 3 };

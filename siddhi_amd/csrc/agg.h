@@ -5,7 +5,8 @@
 // (remove) operand at a time, in the reference's order, so every double sum is
 // the same IEEE result (built with -ffp-contract=off).  Below them the
 // {Max,Min}[Forever]AttributeAggregatorExecutor steps (mm_step): a value and,
-// in tracking mode, the reference's deque, restated with its quirk.
+// in tracking mode, the reference's deque, restated with its quirk; and the
+// {StdDev,DistinctCount,And,Or}AttributeAggregatorExecutor steps (ext_step).
 #pragma once
 #include "engine.h"
 
@@ -212,6 +213,151 @@ __device__ __forceinline__ void mm_step(int kind, int type, bool add, uint64_t x
   flags = (flags & ~(int64_t)1) | (has ? 1 : 0);
   ob = has ? val : 0;
   on = !has;
+}
+
+// ---------------------------------------------------------------- stdDev / distinctCount / and / or
+// {StdDev,DistinctCount,And,Or}AttributeAggregatorExecutor.java.  They use the
+// three state scalars as follows (d, l, c of the fold):
+//   stdDev         d = sum, l = the bits of stdDeviation, c = count; the mean is
+//                  not stored: whenever count >= 1 the reference's mean is the
+//                  double sum / count of exactly these two values
+//   and / or       l = trueEventsCount, c = falseEventsCount
+//   distinctCount  l = the count of the null key, c = the number of other keys;
+//                  the keys are a list of (key bits, count) pairs in the list
+//                  store, sorted by key bits
+__device__ __forceinline__ bool agg_is_ext(int kind) { return kind >= SHD_AGG_STDDEV; }
+
+// StdDevAttributeAggregatorExecutor.java:157-231 (Welford's update, add and
+// remove), :115-133 (a null argument returns currentValue()).  Every operation
+// is one correctly rounded IEEE operation in the reference's order; a negative
+// stdDeviation residue gives NaN from the square root, as Math.sqrt does.
+__device__ __forceinline__ void sd_step(int type, bool add, uint64_t xb, bool xn, double& sum, int64_t& sdb,
+                                        int64_t& c, uint64_t& ob, bool& on) {
+  double sd = __longlong_as_double(sdb);
+  if (!xn) {
+    double v;
+    switch (type) {   // (double) of the unboxed Integer / Long / Float (:237-300)
+      case SHD_T_INT: v = (double)v_i32(xb); break;
+      case SHD_T_LONG: v = (double)(int64_t)xb; break;
+      case SHD_T_FLOAT: v = (double)v_f32(xb); break;
+      default: v = v_f64(xb);
+    }
+    // the mean before this step: sum / count as the last step computed it
+    // (0.0 at count 0, where every field is zeroed)
+    const double old_mean = c == 0 ? 0.0 : __ddiv_rn(sum, (double)c);
+    if (add) {
+      c++;                               // :159
+      if (c == 1) {                      // :162-165
+        sum = v;
+        sd = 0.0;
+      } else if (c != 0) {               // :166-171
+        sum = __dadd_rn(sum, v);
+        const double mean = __ddiv_rn(sum, (double)c);
+        sd = __dadd_rn(sd, __dmul_rn(__dsub_rn(v, old_mean), __dsub_rn(v, mean)));
+      }
+    } else {
+      c--;                               // :176
+      if (c == 0) {                      // :177-180
+        sum = 0.0;
+        sd = 0.0;
+      } else {                           // :181-186
+        sum = __dsub_rn(sum, v);
+        const double mean = __ddiv_rn(sum, (double)c);
+        sd = __dsub_rn(sd, __dmul_rn(__dsub_rn(v, old_mean), __dsub_rn(v, mean)));
+      }
+    }
+  }
+  sdb = __double_as_longlong(sd);
+  // null at count 0, 0.0 at count 1, else Math.sqrt(stdDeviation / count) (:224-231)
+  on = c == 0;
+  ob = (on || c == 1) ? p_f64(0.0) : p_f64(__dsqrt_rn(__ddiv_rn(sd, (double)c)));
+}
+
+// {And,Or}AttributeAggregatorExecutor.java:98-144.  The reference unboxes a
+// null argument and fails the call; here it leaves the counters alone.
+__device__ __forceinline__ void bool_step(int kind, bool add, uint64_t xb, bool xn, int64_t& nt, int64_t& nf,
+                                          uint64_t& ob, bool& on) {
+  if (!xn) {
+    if (xb & 1) nt += add ? 1 : -1;
+    else nf += add ? 1 : -1;
+  }
+  ob = kind == SHD_AGG_AND ? (nt > 0 && nf == 0) : (nt > 0);   // computeLogicalOperation (:142-144)
+  on = false;
+}
+
+// What equals() / hashCode() of the boxed key compare: mm_bits for the numeric
+// types, the dictionary id of a String, the value of a Boolean.
+__device__ __forceinline__ uint64_t dc_key(int type, uint64_t a) {
+  switch (type) {
+    case SHD_T_INT: case SHD_T_LONG: case SHD_T_FLOAT: case SHD_T_DOUBLE: return mm_bits(type, a);
+    case SHD_T_BOOL: return a & 1;
+    default: return (uint64_t)(uint32_t)a;
+  }
+}
+
+// DistinctCountAttributeAggregatorExecutor.java:105-131: a HashMap<Object, Long>
+// as a list of (key, count) pairs sorted by key bits in w[h, t) of the lane's
+// region (two words a pair; an add creates at most one).  Find is a binary
+// search; a new key opens its gap, and a key whose count reaches 0 closes it,
+// from the shorter side -- linear in the list in the worst case.  Null is a key
+// (HashMap allows it): its count is nnull.  Removing a key that is not there
+// throws in the reference; no supported plan does it, here it is a no-op.
+__device__ __forceinline__ void dc_step(int type, bool add, uint64_t xb, bool xn, int64_t& nnull, int64_t& nkeys,
+                                        MmDeque* q, uint64_t& ob, bool& on) {
+  if (xn) {
+    if (add) nnull++;
+    else if (nnull > 0) nnull--;
+  } else if (q) {
+    const uint64_t k = dc_key(type, xb);
+    int64_t lo = 0, n = (q->t - q->h) >> 1;
+    while (lo < n) {   // the first pair whose key is not below k
+      const int64_t mid = (lo + n) >> 1;
+      if (q->w[q->h + 2 * mid] < k) lo = mid + 1;
+      else n = mid;
+    }
+    int64_t i = q->h + 2 * lo;
+    const bool found = i < q->t && q->w[i] == k;
+    if (add && found) {
+      q->w[i + 1]++;                                     // put(data, ++preVal) (:107-108)
+    } else if (add) {
+      // put(data, 1L) (:110): the region holds the carried pairs plus one per
+      // operation, so one side always has room
+      const bool left = q->h >= 2 && (i - q->h <= q->t - i || q->t + 2 > q->room);
+      if (left) {
+        for (int64_t j = q->h; j < i; j++) q->w[j - 2] = q->w[j];
+        q->h -= 2;
+        i -= 2;
+      } else if (q->t + 2 <= q->room) {
+        for (int64_t j = q->t - 1; j >= i; j--) q->w[j + 2] = q->w[j];
+        q->t += 2;
+      } else {
+        i = -1;
+      }
+      if (i >= 0) {
+        q->w[i] = k;
+        q->w[i + 1] = 1;
+      }
+    } else if (found && --q->w[i + 1] == 0) {            // remove(data) at 0 (:124-129)
+      if (i - q->h <= q->t - 2 - i) {
+        for (int64_t j = i + 1; j >= q->h + 2; j--) q->w[j] = q->w[j - 2];
+        q->h += 2;
+      } else {
+        for (int64_t j = i; j + 2 < q->t; j++) q->w[j] = q->w[j + 2];
+        q->t -= 2;
+      }
+    }
+    nkeys = (q->t - q->h) >> 1;
+  }
+  ob = (uint64_t)(nkeys + (nnull > 0 ? 1 : 0));          // distinctValues.size() (:167-169)
+  on = false;
+}
+
+// One step of a stdDev / distinctCount / and / or state.
+__device__ __forceinline__ void ext_step(int kind, int type, bool add, uint64_t xb, bool xn, double& d, int64_t& l,
+                                         int64_t& c, MmDeque* q, uint64_t& ob, bool& on) {
+  if (kind == SHD_AGG_STDDEV) sd_step(type, add, xb, xn, d, l, c, ob, on);
+  else if (kind == SHD_AGG_DISTINCT_COUNT) dc_step(type, add, xb, xn, l, c, q, ob, on);
+  else bool_step(kind, add, xb, xn, l, c, ob, on);
 }
 
 }  // namespace

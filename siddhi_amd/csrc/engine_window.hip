@@ -12,7 +12,9 @@
 //     :271-313 (processInBatchNoGroupBy), :315-373 (processInBatchGroupBy)
 //   query/selector/attribute/aggregator/{Sum,Avg,Count}AttributeAggregatorExecutor.java
 //   query/selector/attribute/aggregator/{Max,Min,MaxForever,MinForever}AttributeAggregatorExecutor.java
-//     (every plan with one of these runs here: k_xw_fold<true> and the deque store)
+//     (every plan with one of these runs here: k_xw_fold<true> and the list store)
+//   query/selector/attribute/aggregator/{StdDev,DistinctCount,And,Or}AttributeAggregatorExecutor.java
+//     (k_xw_fold<true, true>; distinctCount keeps its keys in the list store)
 //   partition/PartitionStreamReceiver.java:175-216 (same-key runs = chunks)
 //   util/snapshot/state/PartitionStateHolder.java:43-69 (state per (partition key,
 //     group key); a window state is dropped when its queue empties)
@@ -478,6 +480,10 @@ struct FoldArgsX {
   uint64_t* dq_work;
   uint32_t* dq_nlen;
   uint32_t* dq_nsrc;
+  // The same store holds distinctCount's keys, (key bits, count) pairs sorted
+  // by key (agg.h dc_step): dq_esz[d] = words an add can append to row d (1 a
+  // deque value, 2 a pair).  stdDev / and / or keep the three scalars only.
+  int dq_esz[kMaxAggs];
 };
 constexpr uint32_t kDqWork = 0x80000000u;
 
@@ -493,8 +499,9 @@ __device__ __forceinline__ void agg_value(int kind, uint64_t ob, bool on, int64_
 // is tracked on the fly: a run = the state's consecutive operations of one
 // chunk; its first and last selected ("on") operations decide the row.
 // MM: the plan has min / max aggregators (the plain instance is the kernel
-// the sum / avg / count plans have always run).
-template <bool MM>
+// the sum / avg / count plans have always run).  XA: it has stdDev /
+// distinctCount / and / or (k_xw_fold<true, true>: MM is set with it).
+template <bool MM, bool XA = false>
 __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict__ ap, const uint32_t* heads,
                                                     int64_t nheads, const uint32_t* ssid, const uint32_t* sq) {
   const FoldArgsX& a = *ap;
@@ -519,7 +526,7 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
         dq[k].w = a.dq_work + a.dq_woff[hh * a.ndq + k];
         dq[k].h = 0;
         dq[k].t = n0;
-        dq[k].room = n0 + (q1 - q0);
+        dq[k].room = n0 + (q1 - q0) * (XA ? a.dq_esz[k] : 1);
         for (int64_t i = 0; i < n0; i++) dq[k].w[i] = src[i];
       }
     }
@@ -535,7 +542,8 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
         ep = a.op_epoch[q];
         for (int g = 0; g < a.nagg; g++) {
           if constexpr (MM) {
-            // reset(): min / max clear value and deque, the Forever kinds keep theirs
+            // reset(): min / max clear value and deque, the Forever kinds keep theirs;
+            // stdDev / distinctCount / and / or clear everything, the key list too
             if (a.kind[g] == SHD_AGG_MAX_FOREVER || a.kind[g] == SHD_AGG_MIN_FOREVER) continue;
             if (a.dq[g] >= 0) dq[a.dq[g]].h = dq[a.dq[g]].t;
           }
@@ -551,7 +559,9 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
         bool on;
         const uint64_t xb = a.argv[(int64_t)g * a.cap + it];
         const bool xn = a.argn[(int64_t)g * a.cap + it] != 0;
-        if (MM && agg_is_minmax(a.kind[g])) {
+        if (XA && agg_is_ext(a.kind[g])) {
+          ext_step(a.kind[g], a.type[g], add, xb, xn, d[g], l[g], c[g], a.dq[g] >= 0 ? &dq[a.dq[g]] : nullptr, ob, on);
+        } else if (MM && agg_is_minmax(a.kind[g])) {
           uint64_t v = (uint64_t)l[g];
           mm_step(a.kind[g], a.type[g], add, xb, xn, v, c[g], a.dq[g] >= 0 ? &dq[a.dq[g]] : nullptr, ob, on);
           l[g] = (int64_t)v;
@@ -603,16 +613,21 @@ __global__ __launch_bounds__(kBlock) void k_xw_fold(const FoldArgsX* __restrict_
   }
 }
 
-// Room of each lane's deque regions: the carried deque plus one slot per
-// operation of the state in this push (an add appends at most one value).
+// Room of each lane's list regions: the carried list plus, per operation of
+// the state in this push, what an add can append (esz: one deque value, or one
+// (key, count) pair).
+struct DqEsz {
+  int v[kMaxAggs];
+};
 __global__ __launch_bounds__(kBlock) void k_xw_dq_room(const uint32_t* heads, int64_t nheads, int64_t nops,
-                                                       const uint32_t* ssid, int ndq, int64_t nstates,
+                                                       const uint32_t* ssid, int ndq, DqEsz esz, int64_t nstates,
                                                        const uint32_t* dq_len, uint32_t* room) {
   for (int64_t hh = (int64_t)blockIdx.x * kBlock + threadIdx.x; hh < nheads; hh = nheads) {
     const int64_t q0 = heads[hh];
     const int64_t q1 = hh + 1 < nheads ? (int64_t)heads[hh + 1] : nops;
     const uint32_t sid = ssid[q0];
-    for (int k = 0; k < ndq; k++) room[hh * ndq + k] = dq_len[(int64_t)k * nstates + sid] + (uint32_t)(q1 - q0);
+    for (int k = 0; k < ndq; k++)
+      room[hh * ndq + k] = dq_len[(int64_t)k * nstates + sid] + (uint32_t)(q1 - q0) * (uint32_t)esz.v[k];
   }
 }
 
@@ -1387,9 +1402,13 @@ struct WindowXEngine : Engine {
   // offsets [ndq][nstates], the values packed in slot dq_cur of dq_val
   // (double-buffered like the items: a push reads one slot and packs what is
   // left into the other, which grows by doubling).
-  bool mm = false, track = false;
-  int ndq = 0;
+  // `xa`: the plan has stdDev / distinctCount / and / or (k_xw_fold<true, true>); each
+  // distinctCount owns a row of the store too, its (key, count) pairs
+  // (dq_esz: the words an add can append to a row).
+  bool mm = false, track = false, xa = false;
+  int ndq = 0, dq_words = 0;
   int dq_of[kMaxAggs] = {};
+  int dq_esz[kMaxAggs] = {};
   DevBuf dq_len, dq_off, dq_val[2];
   int dq_cur = 0;
   int64_t dq_total = 0;
@@ -2317,7 +2336,7 @@ struct WindowXEngine : Engine {
       const int64_t nheads = scan(ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops);
       ohl.reserve(std::max<int64_t>(nheads, 1) * 4);
       launch(k_head_list, nops, ohead.as<uint32_t>(), ohoff.as<uint32_t>(), nops, ohl.as<uint32_t>());
-      if (!mm) {
+      if (!mm && !xa) {
         launch(k_xw_fold<false>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
       } else {
         fold_minmax(fa, nheads, ssid, sq);
@@ -2328,8 +2347,9 @@ struct WindowXEngine : Engine {
     P.nrows = scan_u8_flags(rowflag.as<uint8_t>(), nops);
   }
 
-  // The fold of a plan with min / max aggregators.  Tracking deques: every
-  // lane (a state with operations in this push) gets one region per deque,
+  // The fold of a plan with min / max (or stdDev / distinctCount / and / or)
+  // aggregators.  Tracking deques and distinctCount key lists: every
+  // lane (a state with operations in this push) gets one region per list,
   // sized by its carried length plus its operations and placed by one
   // exclusive scan, so no lane allocates or waits; after the fold the deques of
   // all states -- folded ones from the work area, the rest from the old slot --
@@ -2339,13 +2359,15 @@ struct WindowXEngine : Engine {
     const int64_t ncell = (int64_t)ndq * nstates;
     fa.ndq = ndq;
     for (int g = 0; g < nagg; g++) fa.dq[g] = dq_of[g];
+    DqEsz esz{};
+    for (int k = 0; k < ndq; k++) esz.v[k] = fa.dq_esz[k] = dq_esz[k];
     if (ndq > 0) {
-      if ((int64_t)ndq * nops + dq_total >= (int64_t)INT32_MAX)
-        throw Error(SHD_E_CAPACITY, "min / max deques exceed 2^31 values");
+      if ((int64_t)dq_words * nops + dq_total >= (int64_t)INT32_MAX)
+        throw Error(SHD_E_CAPACITY, "aggregator lists (min / max deques, distinctCount keys) exceed 2^31 values");
       const int64_t nr = nheads * ndq;
       dq_room.reserve(nr * 4);
       dq_woff.reserve(nr * 4);
-      launch(k_xw_dq_room, nheads, ohl.as<uint32_t>(), nheads, nops, ssid, ndq, nstates, dq_len.as<uint32_t>(),
+      launch(k_xw_dq_room, nheads, ohl.as<uint32_t>(), nheads, nops, ssid, ndq, esz, nstates, dq_len.as<uint32_t>(),
              dq_room.as<uint32_t>());
       const int64_t wtotal = scan(dq_room.as<uint32_t>(), dq_woff.as<uint32_t>(), nr);
       dq_work.reserve(std::max<int64_t>(wtotal, 1) * 8);
@@ -2363,7 +2385,8 @@ struct WindowXEngine : Engine {
       fa.dq_nlen = dq_nlen.as<uint32_t>();
       fa.dq_nsrc = dq_nsrc.as<uint32_t>();
     }
-    launch(k_xw_fold<true>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
+    if (xa) launch(k_xw_fold<true, true>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
+    else launch(k_xw_fold<true>, nheads, dev_args(fa), ohl.as<uint32_t>(), nheads, ssid, sq);
     if (ndq == 0) return;
     const int64_t ntotal = scan(dq_nlen.as<uint32_t>(), dq_noff.as<uint32_t>(), ncell);
     const int oth = dq_cur ^ 1;
@@ -2688,11 +2711,30 @@ std::unique_ptr<Engine> make_window_x_engine(const Plan& p, std::string& why) {
   for (int g = 0; g < e->nagg; g++) {
     const auto& a = p.aggs[g];
     e->dq_of[g] = -1;
-    if (a.kind < SHD_AGG_SUM || a.kind > SHD_AGG_MIN_FOREVER) { why = "unknown aggregator"; return nullptr; }
+    if (a.kind < SHD_AGG_SUM || a.kind > SHD_AGG_OR) { why = "unknown aggregator"; return nullptr; }
     if (a.kind < SHD_AGG_MAX) continue;
+    if (a.kind >= SHD_AGG_STDDEV) {
+      // stdDev of a number, and / or of a BOOL, distinctCount of anything a slot holds
+      const bool num = a.type >= SHD_T_INT && a.type <= SHD_T_DOUBLE;
+      const bool ok = a.kind == SHD_AGG_STDDEV ? num
+                      : a.kind == SHD_AGG_DISTINCT_COUNT ? (num || a.type == SHD_T_STRING || a.type == SHD_T_BOOL)
+                                                         : a.type == SHD_T_BOOL;
+      if (a.expr < 0 || !ok) { why = "stdDev / distinctCount / and / or of an argument of this type"; return nullptr; }
+      e->xa = true;
+      if (a.kind == SHD_AGG_DISTINCT_COUNT) {
+        e->dq_esz[e->ndq] = 2;
+        e->dq_words += 2;
+        e->dq_of[g] = e->ndq++;
+      }
+      continue;
+    }
     if (a.expr < 0 || a.type < SHD_T_INT || a.type > SHD_T_DOUBLE) { why = "min / max of a non-numeric argument"; return nullptr; }
     e->mm = true;
-    if (e->track && (a.kind == SHD_AGG_MAX || a.kind == SHD_AGG_MIN)) e->dq_of[g] = e->ndq++;
+    if (e->track && (a.kind == SHD_AGG_MAX || a.kind == SHD_AGG_MIN)) {
+      e->dq_esz[e->ndq] = 1;
+      e->dq_words += 1;
+      e->dq_of[g] = e->ndq++;
+    }
   }
   e->partitioned = !p.part_keys.empty();
   if (e->partitioned) {

@@ -460,8 +460,10 @@ def window_of(qp) -> Optional[Tuple[str, int]]:
     from . import planner as pl
     if any(a[0] > pl.AGG_COUNT for a in qp.plan.aggs):
         # their deques depend on values that left the window long ago, the
-        # Forever kinds on the whole stream: a halo does not rebuild that state
-        raise pl.UnsupportedPlanException("slices with a halo cannot rebuild min / max aggregator state")
+        # Forever kinds on the whole stream, stdDev keeps floating-point residue of every value that
+        # ever passed (§4.4.2): a halo does not rebuild that state
+        raise pl.UnsupportedPlanException("slices with a halo cannot rebuild min / max / stdDev / distinctCount / "
+                                          "and / or aggregator state")
     for h in qp.plan.handlers:
         if h[0] == pl.H_WINDOW:
             if h[1] not in (pl.W_LENGTH, pl.W_TIME):

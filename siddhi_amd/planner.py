@@ -16,7 +16,7 @@ Restates the reference planning rules the hot path depends on:
 * aggregator return types (SumAttributeAggregatorExecutor.java:84-134: INT/LONG
   -> LONG, FLOAT/DOUBLE -> DOUBLE; avg -> DOUBLE; count -> LONG; min / max /
   minForever / maxForever -> the argument's type, MaxAttributeAggregatorExecutor
-  .java:97).
+  .java:97; stdDev -> DOUBLE, distinctCount -> LONG, and / or -> BOOL).
 """
 from __future__ import annotations
 
@@ -51,6 +51,10 @@ AGG_SUM, AGG_AVG, AGG_COUNT = 1, 2, 3
 AGG_MAX, AGG_MIN, AGG_MAX_FOREVER, AGG_MIN_FOREVER = 4, 5, 6, 7
 # function name (lower case) -> kind: the aggregators that return their argument's type
 _MINMAX_KIND = {"max": AGG_MAX, "min": AGG_MIN, "maxforever": AGG_MAX_FOREVER, "minforever": AGG_MIN_FOREVER}
+AGG_STDDEV, AGG_DISTINCT_COUNT, AGG_AND, AGG_OR = 8, 9, 10, 11
+# function name (lower case) -> (kind, return type): the aggregators with a fixed return type
+_FIXED_KIND = {"stddev": (AGG_STDDEV, T_DOUBLE), "distinctcount": (AGG_DISTINCT_COUNT, T_LONG),
+               "and": (AGG_AND, T_BOOL), "or": (AGG_OR, T_BOOL)}
 UNKNOWN_STATE = -1
 NUMERIC_RANK = {T_INT: 0, T_LONG: 1, T_FLOAT: 2, T_DOUBLE: 3}
 ARITH_OPS = {"+": OP_ADD, "-": OP_SUB, "*": OP_MUL, "/": OP_DIV, "%": OP_MOD}
@@ -377,6 +381,32 @@ class ExprCompiler:
                 self.plan.aggs.append((_MINMAX_KIND[name], arg, at))
                 code.append((OP_AGG, len(self.plan.aggs) - 1, 0, 0))
                 return at
+            if e.namespace is None and name in _FIXED_KIND:
+                # {StdDev,DistinctCount,And,Or}AttributeAggregatorExecutor.init (C/query/selector/
+                # attribute/aggregator/StdDevAttributeAggregatorExecutor.java:81-107, DistinctCount...
+                # :88-102, And... :83-96): exactly one parameter, else the app's creation fails.
+                # stdDev of a non-numeric argument fails creation too; and / or of a non-BOOL argument
+                # create in the reference and then fail every event (ClassCastException), a distinctCount
+                # key that is an OBJECT has no device form: both are outside the hot path
+                if not self.agg_allowed:
+                    raise SiddhiAppValidationException("aggregator %s not allowed here" % e.name)
+                if len(e.args) != 1:
+                    raise SiddhiAppCreationException("%s aggregator has to have exactly 1 parameter, currently %d "
+                                                     "parameters provided" % (e.name, len(e.args)))
+                kind, rt = _FIXED_KIND[name]
+                sub = ExprCompiler(self.plan, self.dict, self.metas, self.state_query)
+                arg, at = sub.compile(e.args[0], cs, di)
+                if kind == AGG_STDDEV and at not in NUMERIC_RANK:
+                    raise SiddhiAppCreationException("%s not supported for %s" % (e.name, TYPE_NAME.get(at)))
+                if kind in (AGG_AND, AGG_OR) and at != T_BOOL:
+                    raise UnsupportedPlanException("%s of a %s argument is outside the hot path"
+                                                   % (e.name, TYPE_NAME.get(at)))
+                if kind == AGG_DISTINCT_COUNT and at not in (T_INT, T_LONG, T_FLOAT, T_DOUBLE, T_STRING, T_BOOL):
+                    raise UnsupportedPlanException("distinctCount of a %s argument is outside the hot path"
+                                                   % TYPE_NAME.get(at))
+                self.plan.aggs.append((kind, arg, at))
+                code.append((OP_AGG, len(self.plan.aggs) - 1, 0, 0))
+                return rt
             if e.namespace is None and name == "eventtimestamp" and not e.args:
                 code.append((OP_TS, 0, IDX_CURRENT, 0))
                 return T_LONG
@@ -662,7 +692,7 @@ def _plan_selector(plan: Plan, q: qc.Query, ec: ExprCompiler, metas: List[Meta],
     return names, types
 
 
-_AGG_FUNCS = ("sum", "avg", "count") + tuple(_MINMAX_KIND)
+_AGG_FUNCS = ("sum", "avg", "count") + tuple(_MINMAX_KIND) + tuple(_FIXED_KIND)
 _INSTANCE_OF = {"instanceofboolean": T_BOOL, "instanceofdouble": T_DOUBLE, "instanceoffloat": T_FLOAT,
                 "instanceofinteger": T_INT, "instanceoflong": T_LONG, "instanceofstring": T_STRING}
 
@@ -679,16 +709,17 @@ def _has_agg(e) -> bool:
     return False
 
 
-def _has_minmax(e) -> bool:
-    """Whether an expression holds a min / max / minForever / maxForever aggregator."""
+def _has_fold_only_agg(e) -> bool:
+    """Whether an expression holds an aggregator of a kind above count (min / max / minForever /
+    maxForever, stdDev, distinctCount, and, or): the ones only the keyed window engine folds."""
     if isinstance(e, qc.Func):
-        if e.namespace is None and e.name.lower() in _MINMAX_KIND:
+        if e.namespace is None and (e.name.lower() in _MINMAX_KIND or e.name.lower() in _FIXED_KIND):
             return True
-        return any(_has_minmax(a) for a in e.args)
+        return any(_has_fold_only_agg(a) for a in e.args)
     if isinstance(e, qc.BinOp):
-        return _has_minmax(e.left) or _has_minmax(e.right)
+        return _has_fold_only_agg(e.left) or _has_fold_only_agg(e.right)
     if isinstance(e, (qc.Not, qc.IsNull)):
-        return _has_minmax(e.expr)
+        return _has_fold_only_agg(e.expr)
     return False
 
 
@@ -1180,8 +1211,9 @@ def share_signature(q: qc.Query) -> Optional[str]:
     if isinstance(q.input, qc.StateInput) and (sel.group_by or sel.having is not None or
                                                any(_has_agg(oa.expr) for oa in sel.attrs)):
         return None   # aggregating / having selectors over state output run per query (IR POST section)
-    if any(_has_minmax(oa.expr) for oa in sel.attrs) or (sel.having is not None and _has_minmax(sel.having)):
-        return None   # min / max run on the keyed window engine alone: no shared segmented-scan pass
+    if any(_has_fold_only_agg(oa.expr) for oa in sel.attrs) or \
+            (sel.having is not None and _has_fold_only_agg(sel.having)):
+        return None   # kinds above count run on the keyed window engine alone: no shared segmented-scan pass
     import copy
     if _e1_site(q) is not None:
         q2 = copy.deepcopy(q)
